@@ -17,10 +17,15 @@ Frames are independent units, so ranks shard them with no data-path collective (
 scaling); the exchanges are the all-reduce of the error counters and, in the Monte-Carlo
 leg, one all-reduce of the round's per-realisation error counts.
 
-After the timed region (outside it) every run also does a short Monte-Carlo leg -- BASELINE
+A plain run sets up, warms up, times --steps steps and prints the headline.  With --full,
+after the timed region (outside it) the run also does a short Monte-Carlo leg -- BASELINE
 config[3]: fresh random birefringence + amplifier ASE per realisation, through
 mc.ShardedBer (realisation r on rank r mod G, one all-reduce per round, host replay of
-ber_estimate.m:116-141) -- and reports realisations/s including the reduce in "mc".
+ber_estimate.m:116-141) -- and reports realisations/s including the reduce in "mc"; and
+the other side measurements (CPU baselines, BASELINE configs 2 and 4, one-frame latency,
+reference front end, gateway tier, clock and power during the timed region).
+--dump-outputs DIR writes what the last timed step computed (inputs are the same from run
+to run for the same arguments), so that two builds can be compared output for output.
 
 Prints ONE JSON line on rank 0.
 """
@@ -45,6 +50,9 @@ HBM_COPY_GBS = 6290.0          # same guide: measured float4 copy (79 % of spec)
 INPLACE_RW_GBS = 5100.0        # scripts/experiments/micro/seg_copy.hip: in-place read-modify-write of this access pattern
 SWEEP_BYTES = 64.0             # one sweep over a dual-pol complex128 field: 32 B read + 32 B written per sample
 SURVEY_BYTES_PER_SAMPLE_STEP = 272.0   # FOUR sweeps + 16 B of tables (an upper-bound budget, not what runs)
+DUMP_CAPS = {"bit_errors": 2e6, "symbols": 40e6, "field": 20e6}   # --dump-outputs: bytes per array (the default line's
+                                                                   # 1024 frames of symbols are 33.6 MB: whole)
+DUMP_SEED = 20261015
 
 
 def parse():
@@ -105,7 +113,24 @@ def parse():
                          "--frames 32) and config[4] (--nsymb 16384 --frames 8 --spans 40 --power-ladder --ladder-world 8) AS STATED, each "
                          "with its own roofline and CPU baseline, into \"configs\" of the same JSON line; auto: when the headline is the "
                          "default workload on one GPU")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run the side measurements the options above tune: the Monte-Carlo leg, the one-frame "
+                         "latency, the line with the reference's own front end, the gateway tier, the CPU baselines, --configs, and the "
+                         "clock / power sampling of the timed region.  Without it a run sets up, warms up, times --steps steps and prints "
+                         "the headline line (the side measurements' fields are null or absent)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last step computed (rank 0) as DIR/<name>.npy, float64: bit_errors "
+                         "[channel-frame, pol] (--mc: [channel-frame], pol swap and pi/2 resolved), symbols [channel-frame, pol, "
+                         "symbol, re/im], field [frame, pol, (channel,) sample, re/im] "
+                         "(the fibre's output; pick front end only).  At most %.0f MB in all: an array over its cap is a fixed, seeded "
+                         "sample of its frames (and of a frame's values, when one frame is over it)" % (sum(DUMP_CAPS.values()) / 1e6))
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not a.full:                   # a plain run: the headline only
+        a.mc_rounds, a.configs = 0, "no"
+        a.no_single_frame = a.no_cohmix_line = a.no_gateway = a.no_cpu_baseline = True
+    return a
 
 
 # ------------------------------------------------------------------------------------- launcher ---
@@ -530,6 +555,29 @@ def offline_traffic(fused, F, n, nch=1, flag="g-s-"):
     return None, None
 
 
+def dump_outputs(d, arrays):
+    """--dump-outputs: each entry of `arrays` (name -> tensor, or a tuple of equal-shaped tensors stacked on axis 1, with
+    frames on axis 0) goes to d/<name>.npy as float64, complex values as a trailing (re, im) axis.  An array larger than
+    its DUMP_CAPS entry is a seeded sample of its frames (in frame order), flattened to [frame, value] and sampled in its
+    values too when one frame alone is over the cap: the same arguments give the same sample."""
+    import torch
+    os.makedirs(d, exist_ok=True)
+    for name, ts in arrays.items():
+        ts = ts if isinstance(ts, tuple) else (ts,)
+        rng = np.random.default_rng(DUMP_SEED)
+        F = ts[0].shape[0]
+        frame_bytes = sum(t[0].numel() * (16 if t.is_complex() else 8) for t in ts)
+        k = int(max(1, min(F, DUMP_CAPS[name] // frame_bytes)))
+        idx = None if k == F else torch.as_tensor(np.sort(rng.choice(F, k, replace=False)), device=ts[0].device)
+        parts = [(t if idx is None else t.index_select(0, idx)).cpu() for t in ts]
+        x = torch.stack(parts, 1) if len(parts) > 1 else parts[0]
+        x = (torch.view_as_real(x) if x.is_complex() else x).to(torch.float64).numpy()
+        if x.nbytes > DUMP_CAPS[name]:
+            x = x.reshape(k, -1)
+            x = x[:, np.sort(rng.choice(x.shape[1], int(DUMP_CAPS[name] // (8 * k)), replace=False))]
+        np.save(os.path.join(d, name + ".npy"), np.ascontiguousarray(x))
+
+
 class Env:
     """What every line of a run shares: the rank's place in the job, the library binding, where collectives' tensors live."""
 
@@ -616,6 +664,7 @@ def main():
             for k, v in over.items():
                 setattr(b, k, v)
             b.mc_rounds, b.no_single_frame, b.no_gateway, b.no_cohmix_line, b.share_device = 0, True, True, True, "auto"
+            b.dump_outputs = None
             t0 = time.perf_counter()
             leg = run_line(b, E)
             for k in ("mc", "gateway", "n_gpus", "higher_is_better", "scaling", "vs_baseline", "data", "cpu_baseline_all_cores"):
@@ -714,7 +763,7 @@ def run_line(a, E):
         hp.run(ux, uy, noise_sigma=a.noise, noise_seed=1000 * rank + i)
     sync_all()
     hp.kernel_times()                  # (drop the warm-up's kernel intervals)
-    pwatch = PowerWatch().start() if rank == 0 else None
+    pwatch = PowerWatch().start() if (rank == 0 and a.full) else None
     t0 = time.perf_counter()
     # The receiver of a batch is ENQUEUED by a second host thread (its kernels go to the receiver's stream either way): the
     # fibre call blocks its host thread until the step loop has ended, and the ~3 ms it takes to enqueue the receiver's dozen
@@ -804,6 +853,13 @@ def run_line(a, E):
     rxm = sum(ev.elapsed_ms(x, y) for x, y in rx_ms)
     ev.destroy_all()
     ncyc = hp.last_ncycle(F)
+    if a.dump_outputs and rank == 0:
+        # (before the side legs: the one-frame leg and the gateway tier reuse this plan's receiver buffers)
+        CF = F * nch
+        out_arrays = {"bit_errors": hp.errors_resolved(CF) if a.mc else hp.err[:CF], "symbols": hp.sym[:CF]}
+        if hp.front is None:           # (the cohmix front end consumes the field)
+            out_arrays["field"] = (ux, uy)
+        dump_outputs(a.dump_outputs, out_arrays)
 
     # ---- Monte-Carlo leg (BASELINE config[3]; M2 of SURVEY 8d): outside the timed region above, timed on its own ----
     mc_out = None

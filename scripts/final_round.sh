@@ -7,17 +7,17 @@ mkdir -p $O
 export TMPDIR=/tmp
 R=$PWD
 if [ $part = lines ]; then
-  timeout -k 10 600 python3 bench.py > $O/bench_default.json 2> $O/bench_default.err || { tail $O/bench_default.err; exit 1; }
-  timeout -k 10 300 python3 bench.py --no-overlap --no-cpu-baseline --mc-rounds 0 --no-gateway --no-cohmix-line --configs no > $O/bench_no_overlap.json 2>/dev/null || exit 1
-  timeout -k 10 300 python3 bench.py --frontend cohmix --no-cpu-baseline --mc-rounds 0 --no-gateway > $O/bench_cohmix.json 2>/dev/null || exit 1
-  timeout -k 10 300 python3 bench.py --power-ladder --no-cpu-baseline --mc-rounds 0 --no-gateway > $O/bench_ladder.json 2>/dev/null || exit 1
-  timeout -k 10 300 python3 bench.py --mc --no-cpu-baseline --no-gateway > $O/bench_mc.json 2>/dev/null || exit 1
-  timeout -k 10 300 python3 bench.py --nsymb 16384 --frames 16 --steps 4 --warmup 1 --variants 1 --no-cpu-baseline --no-single-frame --mc-rounds 0 --no-gateway > $O/bench_c4_frame.json 2>/dev/null || exit 1
-  timeout -k 10 300 python3 bench.py --nsymb 16384 --frames 16 --steps 4 --warmup 1 --variants 1 --share-device no --no-cpu-baseline --no-single-frame --mc-rounds 0 --no-gateway > $O/bench_c4_frame_fused.json 2>/dev/null || exit 1
-  timeout -k 10 600 python3 bench.py --nsymb 16384 --frames 8 --spans 40 --power-ladder --ladder-world 8 --steps 2 --warmup 1 --variants 1 --no-cpu-baseline --no-single-frame --mc-rounds 0 --no-gateway > $O/bench_c4_40spans.json 2>/dev/null || exit 1
-  timeout -k 10 600 python3 bench.py --nch 16 --spans 10 --nf 5 --frames 32 --steps 3 --warmup 1 --mc-rounds 0 --no-gateway > $O/bench_c2.json 2>/dev/null || exit 1
-  timeout -k 10 300 python3 bench.py --nsymb 4096 --frames 256 --steps 4 --warmup 1 --no-cpu-baseline --no-single-frame --mc-rounds 0 --no-gateway > $O/bench_2pow18.json 2>/dev/null || exit 1
-  timeout -k 10 300 python3 bench.py --nsymb 16384 --flag gps- --frames 16 --steps 3 --warmup 1 --variants 1 --share-device no --no-cpu-baseline --no-single-frame --mc-rounds 0 --no-gateway > $O/bench_2pow20_pmd.json 2>/dev/null || exit 1
+  timeout -k 10 600 python3 bench.py --full > $O/bench_default.json 2> $O/bench_default.err || { tail $O/bench_default.err; exit 1; }
+  timeout -k 10 300 python3 bench.py --full --no-overlap --no-cpu-baseline --mc-rounds 0 --no-gateway --no-cohmix-line --configs no > $O/bench_no_overlap.json 2>/dev/null || exit 1
+  timeout -k 10 300 python3 bench.py --full --frontend cohmix --no-cpu-baseline --mc-rounds 0 --no-gateway > $O/bench_cohmix.json 2>/dev/null || exit 1
+  timeout -k 10 300 python3 bench.py --full --power-ladder --no-cpu-baseline --mc-rounds 0 --no-gateway > $O/bench_ladder.json 2>/dev/null || exit 1
+  timeout -k 10 300 python3 bench.py --full --mc --no-cpu-baseline --no-gateway > $O/bench_mc.json 2>/dev/null || exit 1
+  timeout -k 10 300 python3 bench.py --full --nsymb 16384 --frames 16 --steps 4 --warmup 1 --variants 1 --no-cpu-baseline --no-single-frame --mc-rounds 0 --no-gateway > $O/bench_c4_frame.json 2>/dev/null || exit 1
+  timeout -k 10 300 python3 bench.py --full --nsymb 16384 --frames 16 --steps 4 --warmup 1 --variants 1 --share-device no --no-cpu-baseline --no-single-frame --mc-rounds 0 --no-gateway > $O/bench_c4_frame_fused.json 2>/dev/null || exit 1
+  timeout -k 10 600 python3 bench.py --full --nsymb 16384 --frames 8 --spans 40 --power-ladder --ladder-world 8 --steps 2 --warmup 1 --variants 1 --no-cpu-baseline --no-single-frame --mc-rounds 0 --no-gateway > $O/bench_c4_40spans.json 2>/dev/null || exit 1
+  timeout -k 10 600 python3 bench.py --full --nch 16 --spans 10 --nf 5 --frames 32 --steps 3 --warmup 1 --mc-rounds 0 --no-gateway > $O/bench_c2.json 2>/dev/null || exit 1
+  timeout -k 10 300 python3 bench.py --full --nsymb 4096 --frames 256 --steps 4 --warmup 1 --no-cpu-baseline --no-single-frame --mc-rounds 0 --no-gateway > $O/bench_2pow18.json 2>/dev/null || exit 1
+  timeout -k 10 300 python3 bench.py --full --nsymb 16384 --flag gps- --frames 16 --steps 3 --warmup 1 --variants 1 --share-device no --no-cpu-baseline --no-single-frame --mc-rounds 0 --no-gateway > $O/bench_2pow20_pmd.json 2>/dev/null || exit 1
   cat $O/bench_default.json $O/bench_no_overlap.json $O/bench_cohmix.json $O/bench_ladder.json $O/bench_mc.json $O/bench_c4_frame.json $O/bench_c4_frame_fused.json $O/bench_c4_40spans.json $O/bench_c2.json $O/bench_2pow18.json $O/bench_2pow20_pmd.json > $O/bench.jsonl
   python3 - <<PY
 import json

@@ -9,7 +9,7 @@ timeout -k 10 1000 python -m pytest tests -m gpu -x -q --durations=8 > $O/gpu_te
 [ $rc -eq 0 ] || exit $rc
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || { tail -20 $O/smoke.log; exit 1; }
 tail -1 $O/smoke.log
-timeout -k 10 600 python bench.py > $O/bench_default.json 2> $O/bench_default.err || { tail $O/bench_default.err; exit 1; }
+timeout -k 10 600 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err || { tail $O/bench_default.err; exit 1; }
 python - <<PY
 import json
 d = json.loads(open("$O/bench_default.json").read().strip().splitlines()[-1])

@@ -318,7 +318,7 @@ def test_bench_starts_its_own_ranks():
     import subprocess
     env = dict(os.environ, PLX_BENCH_REHEARSAL="1")
     env.pop("WORLD_SIZE", None); env.pop("RANK", None); env.pop("LOCAL_RANK", None)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0", "--frames", "8",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "1", "--warmup", "0", "--frames", "8",
                           "--nsymb", "256", "--nt", "32", "--variants", "2", "--mc-rounds", "2", "--mc-frames", "4", "--mc-total", "12",
                           "--no-cpu-baseline", "--no-single-frame"], env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -340,7 +340,7 @@ def test_bench_starts_its_own_ranks():
 
 @pytest.mark.gpu
 def test_default_bench_line_carries_configs_2_and_4_as_stated():
-    """The driver runs `python bench.py` with no workload flags: after the headline (BASELINE config[1]) the line must carry bounded
+    """`python bench.py --full` with no workload flags: after the headline (BASELINE config[1]) the line must carry bounded
     legs of config[2] (16 channels x 10 spans x 32 frames) and config[4] (2^20 samples x 40 spans, rank 0's share of the 64-point
     ladder over 8 GPUs) AS STATED, each with value, roofline (HBM and FP64 fractions, offline traffic) and its own CPU baseline."""
     import json
@@ -348,7 +348,7 @@ def test_default_bench_line_carries_configs_2_and_4_as_stated():
     env = dict(os.environ)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "PLX_BENCH_REHEARSAL"):
         env.pop(k, None)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--mc-rounds", "0", "--no-gateway",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--mc-rounds", "0", "--no-gateway",
                           "--no-single-frame", "--no-cohmix-line", "--cpu-frames", "2"], env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -381,7 +381,7 @@ def test_bench_line_carries_the_contract_fields():
     env = dict(os.environ)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "PLX_BENCH_REHEARSAL"):
         env.pop(k, None)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--frames", "32", "--nsymb", "256",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--frames", "32", "--nsymb", "256",
                           "--nt", "64", "--variants", "2", "--mc-rounds", "1", "--mc-frames", "8", "--mc-total", "16", "--cpu-frames", "2"],
                          env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -406,6 +406,63 @@ def test_bench_line_carries_the_contract_fields():
     g = d["gateway"]["plx_cmapolardemux"]
     assert g["passes"] == g["per_pass_mex_loop_passes"] == g["oracle_passes"] and g["allocations_in_repeats"] == 0
     assert "fibre_step" in d["config"] and d["config"]["channels_per_frame"] == 1
+
+
+@pytest.mark.gpu
+def test_plain_bench_line_is_the_headline_and_dumps_the_last_step(tmp_path):
+    """`bench.py` without --full: --steps timed steps and the headline fields, no side measurement; --dump-outputs writes
+    what the last timed step computed as float64 arrays, within 64 MB."""
+    import json
+    import subprocess
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "PLX_BENCH_REHEARSAL"):
+        env.pop(k, None)
+    F, nsymb, nt = 32, 256, 64
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--frames", str(F),
+                          "--nsymb", str(nsymb), "--nt", str(nt), "--variants", "2", "--dump-outputs", str(tmp_path)],
+                         env=env, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["metric"] == "dual-pol Gsample/s through SSFM+Rx-DSP" and d["unit"] == "Gsample/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "f64" and d["steps"] == 3 and d["warmup"] == 1
+    assert d["value"] == pytest.approx(F * nsymb * nt / (d["ms_per_step"] * 1e-3) / 1e9, rel=1e-9)
+    assert d["mc"] is None and d["gateway"] is None and "cpu_baseline" not in d and "configs" not in d
+    c = d["config"]
+    assert c["single_frame"] is None and c["with_reference_front_end"] is None and c["power_state"] is None
+    got = {f: np.load(os.path.join(tmp_path, f)) for f in sorted(os.listdir(tmp_path))}
+    assert set(got) == {"bit_errors.npy", "symbols.npy", "field.npy"}
+    assert sum(os.path.getsize(os.path.join(tmp_path, f)) for f in got) <= 64e6
+    e, s, u = got["bit_errors.npy"], got["symbols.npy"], got["field.npy"]
+    assert e.shape == (F, 2) and s.shape == (F, 2, nsymb, 2) and u.shape == (F, 2, nsymb * nt, 2)
+    assert all(x.dtype == np.float64 and np.isfinite(x).all() for x in (e, s, u))
+    # the last step's per-frame counts are a part of the line's total over the timed steps
+    assert (e == np.round(e)).all() and (e >= 0).all() and (e.sum(0) <= np.array(c["bit_errors_xy"])).all()
+
+
+def test_dump_outputs_samples_within_the_caps(tmp_path, monkeypatch):
+    """bench.dump_outputs: an array within its cap is written whole; one over it is a seeded sample of its frames, and of
+    the values of a frame when one frame alone is over the cap -- the same sample every time."""
+    import bench
+    monkeypatch.setattr(bench, "DUMP_CAPS", {"bit_errors": 1e4, "symbols": 4e4, "field": 3e4})
+    g = torch.Generator().manual_seed(3)
+    err = torch.randint(0, 9, (64, 2), generator=g)
+    sym = torch.randn(64, 2, 32, dtype=torch.complex128, generator=g)
+    ux, uy = (torch.randn(4, 2048, dtype=torch.complex128, generator=g) for _ in range(2))
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"bit_errors": err, "symbols": sym, "field": (ux, uy)})
+    for f in ("bit_errors", "symbols", "field"):
+        x, y = np.load(tmp_path / "a" / (f + ".npy")), np.load(tmp_path / "b" / (f + ".npy"))
+        assert x.dtype == np.float64 and x.nbytes <= bench.DUMP_CAPS[f] and np.array_equal(x, y)
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "bit_errors.npy"), err.numpy())
+    s = np.load(tmp_path / "a" / "symbols.npy")               # 64 frames of 1 KB: 39 of them, in frame order
+    full = torch.view_as_real(sym).numpy()
+    assert s.shape == (39, 2, 32, 2)
+    rows = [int(np.flatnonzero((full == r).all(axis=(1, 2, 3)))[0]) for r in s]
+    assert rows == sorted(set(rows))
+    u = np.load(tmp_path / "a" / "field.npy")                 # one frame of (ux, uy) is 64 KB: a sample of frame values
+    assert u.shape == (1, 3750)
 
 
 def _nccl_worker(q):
