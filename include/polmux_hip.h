@@ -236,6 +236,42 @@ int plx_cde_ofde(const double *xr, const double *xi, const double *yr, const dou
 /* the reference display()s a message and returns [] on bad arguments (:63-85): the
  * gateway returns PLX_ERR_ARG with that message and leaves the outputs untouched.  */
 
+/* ------------------------------------------------- digital backpropagation --- */
+/* The receiver-side inverse of matrix_ssfm (fiber.m:459-555) over a link of nspans identical spans, each but the last
+ * followed by an amplifier of power gain exp(alphalin*L).  Input: the field after the receiver's amplifier (which
+ * restores the last span's loss) in units of scale * sqrt(mW).  u = scale * in; for each span, last first:
+ * u *= exp(-alphalin L / 2), then the span's steps in reverse order, each the exact inverse of one forward step:
+ * u *= exp(+alphalin dz / 2); u = ifft(fft(u) .* exp(+i betat dz)); inverse Kerr step with xi*gam and
+ * leff(dz) = (1 - exp(-alphalin dz)) / alphalin (Manakov: phase +(8/9) xi gam leff (|ux|^2 + |uy|^2); CNLSE: rotation
+ * by -xi gam leff s3 / 3, then phase +xi gam leff P).  Finally out = u / scale.  No PMD (db1 = 0).
+ * Two routes: nfft <= 4096, one workgroup per frame holds the dual-polarisation frame in LDS for the whole link (one
+ * HBM round trip); larger nfft (up to 2^20), or PLX_DBP_STREAMED, the SSFM plan's FFT engine as a spectral filter and
+ * an element-wise Kerr kernel per step.                                                                          */
+typedef struct plx_dbp_desc {
+    int64_t nfft;          /* samples per polarisation, power of two in [256, 2^20]            */
+    int32_t max_frames;    /* batch capacity                                                   */
+    int32_t nspans;        /* >= 1                                                             */
+    int32_t nsteps;        /* steps per span, >= 1                                             */
+    int32_t manakov;       /* 1: Manakov (8/9) nonlinear step, 0: CNLSE                        */
+    double span_length;    /* L [m]                                                            */
+    double alphalin;       /* [1/m] fiber.m:302                                                */
+    double gam;            /* [1/mW/m]                                                         */
+    double xi;             /* fraction of the nonlinearity backpropagated (1 = exact inverse)  */
+    const double *betat;   /* [nfft] host, FFT order (plx_ssfm_desc.betat of one column)       */
+    const double *dz;      /* [nsteps] host, forward order, summing to span_length; NULL: uniform */
+} plx_dbp_desc;
+typedef struct plx_dbp_plan plx_dbp_plan;   /* (plx_dbp is the gateway call) */
+#define PLX_DBP_STREAMED 1u   /* take the streamed route at any nfft */
+int plx_dbp_create(plx_dbp_plan **plan, const plx_dbp_desc *desc, uint32_t flags);
+int plx_dbp_destroy(plx_dbp_plan *plan);
+/* d_in, d_out: [nframes][X|Y][nfft] interleaved complex128 (HotPath.rx's layout), d_in == d_out allowed;
+ * d_scale: [nframes] device doubles or NULL (scale 1) */
+int plx_dbp_apply_dev(plx_dbp_plan *plan, const double *d_in, double *d_out, int nframes, const double *d_scale, void *stream);
+/* gateway: one frame on host arrays with separate re/im planes (xi, yi may be NULL), nx == desc->nfft; the plan is
+ * built for the call (not cached), the staging buffers are the library's                                          */
+int plx_dbp(const double *xr, const double *xi, const double *yr, const double *yi, int64_t nx, const plx_dbp_desc *desc,
+            double scale, double *oxr, double *oxi, double *oyr, double *oyi);
+
 /* -------------------------------------------------- CMA / EASI 2x2 butterfly --- */
 /* [Y,h1,h2] = cmaadaptivefilter(xx,h1,h2,taps,mu,R,sps)  cmaadaptivefilter.c:93-174.
  * xx [Mdim x 2], h1/h2 [taps x 2], y [Mdim-taps+1 x 2]; split planes.  Like the

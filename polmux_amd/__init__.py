@@ -13,8 +13,9 @@ from .rx import (CDE_OFDE, DspPdmCohQpsk, cmaadaptivefilter, easiadaptivefilter,
 from .rxfront import (RxPdmCohQpsk, corrdelay, dsp4cohdec, evaldelay, eye_opening, myfilter,  # noqa: F401
                       mygeteyeinfo, receiver_cohmix)
 from .pmdinv import inverse_pmd  # noqa: F401
+from .dbp import DBP  # noqa: F401
 from .mc import ber_estimate, mc_estimate  # noqa: F401
 
 __all__ = ["PolmuxError", "GSTATE", "CONSTANTS", "reset_all", "create_field", "lasersource", "fiber", "ampliflat", "CDE_OFDE", "receiver_cohmix", "RxPdmCohQpsk", "dsp4cohdec", "myfilter", "evaldelay",
            "DspPdmCohQpsk", "cmaadaptivefilter", "easiadaptivefilter", "fastexp", "samp2pat", "ber_estimate",
-           "mc_estimate", "inverse_pmd"]
+           "mc_estimate", "inverse_pmd", "DBP"]

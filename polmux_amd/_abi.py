@@ -18,6 +18,7 @@ PLX_ERR_UNSUPPORTED = -3
 PLX_ERR_REFERENCE = -4
 PLX_ERR_TIMEOUT = -5
 PLX_SSFM_SHARE_DEVICE = 1
+PLX_DBP_STREAMED = 1
 
 
 class PolmuxError(RuntimeError):
@@ -58,6 +59,12 @@ class FrontDesc(C.Structure):
                 ("adcbits", C.c_int32), ("decim", C.c_int32), ("ntaps", C.c_int32), ("fir", C.c_void_p),
                 ("hopt_re", C.c_void_p), ("hopt_im", C.c_void_p), ("hel_re", C.c_void_p), ("hel_im", C.c_void_p),
                 ("elo_re", C.c_void_p), ("elo_im", C.c_void_p), ("elo_scalar", C.c_double)]
+
+
+class DbpDesc(C.Structure):
+    _fields_ = [("nfft", C.c_int64), ("max_frames", C.c_int32), ("nspans", C.c_int32), ("nsteps", C.c_int32),
+                ("manakov", C.c_int32), ("span_length", C.c_double), ("alphalin", C.c_double), ("gam", C.c_double),
+                ("xi", C.c_double), ("betat", C.c_void_p), ("dz", C.c_void_p)]
 
 
 _vp, _i32, _i64, _dbl, _sz = C.c_void_p, C.c_int32, C.c_int64, C.c_double, C.c_size_t
@@ -101,6 +108,10 @@ SIGNATURES = {
     "plx_cde_destroy": [_vp],
     "plx_cde_apply_dev": [_vp, _vp, _vp, _i64, C.c_int, _vp],
     "plx_cde_ofde": [_vp, _vp, _vp, _vp, _i64, _dbl, _dbl, _dbl, _dbl, _dbl, _i64, _i64, _vp, _vp, _vp, _vp],
+    "plx_dbp_create": [C.POINTER(_vp), C.POINTER(DbpDesc), C.c_uint32],
+    "plx_dbp_destroy": [_vp],
+    "plx_dbp_apply_dev": [_vp, _vp, _vp, C.c_int, _vp, _vp],
+    "plx_dbp": [_vp, _vp, _vp, _vp, _i64, C.POINTER(DbpDesc), _dbl, _vp, _vp, _vp, _vp],
     "plx_cmaadaptivefilter": [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _dbl, _dbl, _vp, _dbl, _vp, _vp],
     "plx_easiadaptivefilter": [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _dbl, _dbl, _dbl, _vp, _vp],
     "plx_cmaadaptivefilter_m": [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _dbl, _vp, _vp, _vp],

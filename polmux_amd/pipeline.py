@@ -37,7 +37,8 @@ class HotPathConfig:
                  dgd=0.1, nplates=100, manakov="no", nspans=1, fft_length=256, cde_L=128, applypol=True,
                  polmethod="cma", cma_taps=7, cma_mu=1 / 6000, freqavg=500, phasavg=3, poworder=2,
                  frontend="pick", oftype="gauss", obw=1.9, oord=3, eftype="bessel5", ebw=0.65, eord=4, lopower=0.0,
-                 adcbits=5, span_nf_db=None, rx_amp=False, variants=1, nch=1, chspacing=0.4, share_device=False):
+                 adcbits=5, span_nf_db=None, rx_amp=False, variants=1, nch=1, chspacing=0.4, share_device=False,
+                 equaliser="cde", dbp_steps=4, dbp_xi=1.0):
         """frontend: 'pick' = 2-sps sampling supplied by the harness; 'cohmix' = the reference's own
         receiver_cohmix + ADC + decimate chain (RxPdmCohQpsk.m, Run_my_PDM_QPSK.m:52-73 defaults) on the device.
         nspans > 1: every span but the last is followed by an in-line flat amplifier restoring its loss
@@ -53,7 +54,11 @@ class HotPathConfig:
         channel has its own receiver (receiver_cohmix.m:104-125 picks the column).
         share_device: the fibre plan takes the barrier-free three-sweep step (plx_ssfm_create_ex, PLX_SSFM_SHARE_DEVICE): a
         frame that is the whole grid of the fused sweep (2^20 samples, 16 channels) can then propagate beside the receiver of
-        the previous batch on another stream (the fused sweep would wait for its frame's workgroups to be co-resident)."""
+        the previous batch on another stream (the fused sweep would wait for its frame's workgroups to be co-resident).
+        equaliser: 'cde' = CDE_OFDE (overlap-save dispersion compensation); 'dbp' = digital backpropagation of the nspans
+        spans on the 2-sps samples (polmux_amd.dbp, plx_dbp_apply_dev) with dbp_steps uniform steps per span and dbp_xi
+        of the nonlinearity, using the reference wavelength's D, S and gamma (WDM channel-frames as well); 'pick' front
+        end only (the cohmix LO/ADC chain is not proportional to the field)."""
         self.__dict__.update(locals())
         del self.__dict__["self"]
 
@@ -65,6 +70,10 @@ class HotPathConfig:
 class HotPath:
     def __init__(self, cfg, max_frames):
         import torch
+        if cfg.equaliser not in ("cde", "dbp"):
+            raise ValueError("equaliser must be 'cde' or 'dbp'")
+        if cfg.equaliser == "dbp" and cfg.frontend != "pick":
+            raise ValueError("equaliser='dbp' needs frontend='pick' (the cohmix LO/ADC chain is not proportional to the field)")
         self.torch = torch
         self.cfg = cfg
         self.F = int(max_frames)
@@ -139,6 +148,17 @@ class HotPath:
         # receive scale: undo the span loss and bring symbols to the 4*sqrt(P) full scale that
         # DspPdmCohQpsk divides by (DspPdmCohQpsk.m:22-23, "2* -> see receiver_cohmix")
         self.rx_scale = 4.0 * math.sqrt(power) / math.sqrt(power / 2.0)
+        self.dbp = None
+        if cfg.equaliser == "dbp":
+            # the 2-sps samples are the field after the receiver's amplifier (physical with rx_amp, else folded into
+            # rx_scale below) times this full-scale factor times rx_gain: DBP's scale maps them back to sqrt(mW)
+            from .dbp import DbpPlan, dbp_betat, dbp_desc
+            self.dbp_scale = 1.0 / self.rx_scale
+            gam_ref = 2 * math.pi * cfg.n2 / (cfg.lam * cfg.aeff) * 1e18                      # fiber.m:325 at lambda
+            bt = dbp_betat(self.Lrx, fs, cfg.lam * 1e-9, cfg.disp * 1e-6, cfg.slope * 1e3) * self.fls[0]
+            self.dbp = DbpPlan(dbp_desc(self.Lrx, self.CF, cfg.nspans, cfg.dbp_steps, str(cfg.manakov).lower() == "yes",
+                                        cfg.length, self.alphalin, gam_ref, cfg.dbp_xi, bt))
+            self._dbp_sc = torch.full((self.CF,), self.dbp_scale, dtype=torch.float64, device=self.dev)
         if not cfg.rx_amp:
             self.rx_scale *= math.exp(0.5 * self.alphalin * cfg.length)
         self.front = None
@@ -168,6 +188,9 @@ class HotPath:
             if h:
                 self.lib.call(name, h)
         self.ssfm = self.cde = self.dsp = None
+        if self.dbp is not None:
+            self.dbp.close()
+            self.dbp = None
         if self.front is not None:
             self.front.close()
             self.front = None
@@ -294,7 +317,14 @@ class HotPath:
             # one frame of rx = [X | Y] contiguous: a single-field, single-"polarisation" ampliflat with unit gain
             self.lib.call("plx_ampliflat_dev", rx.data_ptr(), None, 2 * self.Lrx, 1, F, 1.0, sig.ctypes.data, None,
                           int(noise_seed or 0) & (2 ** 64 - 1), kt.data_ptr() if kt is not None else None, 1, 0, st)
-        self.lib.call("plx_cde_apply_dev", self.cde, rx.data_ptr(), self.eq.data_ptr(), self.Lrx, 2 * F, st)
+        if self.dbp is not None:
+            sc = self._dbp_sc[:F]
+            if self.rx_gain is not None:     # launch-power ladder: rx carries each frame's own gain
+                sc = (sc / self.rx_gain[:F].reshape(-1)).contiguous()
+                self._dbp_sc_keep = sc       # alive until the kernel has run
+            self.dbp.apply(rx, self.eq, sc, st)
+        else:
+            self.lib.call("plx_cde_apply_dev", self.cde, rx.data_ptr(), self.eq.data_ptr(), self.Lrx, 2 * F, st)
         self.lib.call("plx_dsp_run_dev", self.dsp, self.eq.data_ptr(), self.sym.data_ptr(), F, st)
         if self.nvar > 1:     # frames carry different sequences: each compares with its own transmitted bits
             self.lib.call("plx_decide_count_frames_dev", self.sym.data_ptr(), cfg.nsymb, 2, F, self.pat_frames.data_ptr(),
