@@ -98,15 +98,9 @@ struct Adaptive {
     double alphalin;
     int fls2, fls3;
 
-    void lin(cplx *x, double dz)
-    { // lin_step(betat*dz, x): x = ifft(fft(x).*fastexp(-betat*dz))
-        SsfmArgs b = a;
-        b.ux = x; b.uy = nullptr; b.force = 1; b.spm = 0; b.xpm = 0; b.f_cur = dz; b.f_leff = 0; b.f_sc = b.invN;
-        const int N1 = 1 << b.p1, N2 = 1 << b.p2;
-        const dim3 gcol((unsigned)(N2 / b.W), (unsigned)b.nfc), grow((unsigned)(N1 / b.R), (unsigned)b.nfc);
-        launch(col_fwd_kernel(), gcol, dim3(256), P->lds_col, st, b);
-        launch(row_kernel(), grow, dim3((unsigned)P->row_threads), P->lds_row, st, b);
-        launch(col_inv_kernel(), gcol, dim3(256), P->lds_col, st, b);
+    int lin(cplx *x, double dz)
+    { // lin_step(betat*dz, x): x = ifft(fft(x).*fastexp(-betat*dz)), on the row pass the plan chose
+        return plx_ssfm_linear_dev(P, a, x, dz, st);
     }
     void nl_att(cplx *x, double dz)
     { // nl_step(alphalin,gam,dz,x,...) then x = x*exp(-halfalpha*dz)
@@ -116,18 +110,25 @@ struct Adaptive {
         if (g > 2048) g = 2048;
         launch_nl_att(g, st, x, a.gam, P->N, a.nfc, fls2, fls3, leff, att);
     }
-    // one trial of adaptssfm; returns <0 on HIP failure
+    // one trial of adaptssfm; returns -1 on a HIP failure, -2 on a failed linear step (whose message is set)
     int trial(double &zdone, double &dz, double trg_err, double safety, int &nrej, int &ncycle)
     {
         const double dz1 = dz, dz2 = 0.5 * dz1, dz4 = 0.25 * dz1;
         if (hipMemcpyAsync(stack, u, n * sizeof(cplx), hipMemcpyDeviceToDevice, st) != hipSuccess) return -1;
         if (hipMemcpyAsync(uh, u, n * sizeof(cplx), hipMemcpyDeviceToDevice, st) != hipSuccess) return -1;
-        nl_att(u, dz2); lin(u, dz1); nl_att(u, dz2);                                        // :972-979
-        nl_att(uh, dz4); lin(uh, dz2); nl_att(uh, dz2); lin(uh, dz2); nl_att(uh, dz4);      // :983-993
+        nl_att(u, dz2);
+        if (lin(u, dz1)) return -2;
+        nl_att(u, dz2);                                                                     // :972-979
+        nl_att(uh, dz4);
+        if (lin(uh, dz2)) return -2;
+        nl_att(uh, dz2);
+        if (lin(uh, dz2)) return -2;
+        nl_att(uh, dz4);                                                                    // :983-993
         if (hipMemsetAsync(d_max, 0, sizeof(unsigned long long), st) != hipSuccess) return -1;
         unsigned g = (unsigned)((n + 255) / 256);
         if (g > 1024) g = 1024;
         launch_maxdiff(g, st, u, uh, n, d_max);
+        if (hipGetLastError() != hipSuccess) return -1;
         if (hipMemcpyAsync(&h_max, d_max, sizeof(h_max), hipMemcpyDeviceToHost, st) != hipSuccess) return -1;
         if (hipStreamSynchronize(st) != hipSuccess) return -1;
         double emax;
@@ -139,6 +140,7 @@ struct Adaptive {
             nrej = nrej + 1;
         } else {                                                                            // accept :1003-1008
             launch_richardson(g, st, u, uh, n);
+            if (hipGetLastError() != hipSuccess) return -1;
             zdone = zdone + dz1;
             dz = safety * sqrt(trg_err / est_err) * dz1;
             ncycle = ncycle + 1;
@@ -185,6 +187,12 @@ extern "C" int plx_scalar_ssfm_adaptive(double *ur, double *ui, const plx_ssfm_d
     A.d_max = (unsigned long long *)(fld + 3 * n);
     A.a.nframes = 1; A.alphalin = d.alphalin; A.fls2 = d.fls[2]; A.fls3 = d.fls[3];
     auto cleanup = [&]() { P->a = saved; };
+    auto trial_failed = [&](int t) {
+        cleanup();
+        if (t == -1) plx_set_error("plx_scalar_ssfm_adaptive: HIP failure in adaptssfm");
+        else plx_set_error(std::string("plx_scalar_ssfm_adaptive: ") + plx_last_error());
+        return PLX_ERR_HIP;
+    };
     if (hipMemcpy(A.u, h, n * sizeof(cplx), hipMemcpyHostToDevice) != hipSuccess ||
         hipMemset(P->d_ctl, 0, sizeof(FrameCtl)) != hipSuccess || hipMemset(P->d_ndone, 0, 64) != hipSuccess ||
         hipMemset(P->d_umax, 0, sizeof(unsigned long long) * d.nfc) != hipSuccess) {
@@ -216,7 +224,7 @@ extern "C" int plx_scalar_ssfm_adaptive(double *ur, double *ui, const plx_ssfm_d
         double zdone = 0;
         while (zdone < Lf) {
             if (zdone + dz > Lf) dz = Lf - zdone;
-            if (A.trial(zdone, dz, ltol, safety, nrej, ncycle)) { cleanup(); PLX_FAIL(PLX_ERR_HIP, "plx_scalar_ssfm_adaptive: HIP failure in adaptssfm"); }
+            if (int t = A.trial(zdone, dz, ltol, safety, nrej, ncycle)) return trial_failed(t);
             if (dz > d.dzmaxt) dz = d.dzmaxt;
         }
         rc = (hipMemcpy(h, A.u, n * sizeof(cplx), hipMemcpyDeviceToHost) == hipSuccess) ? PLX_OK : PLX_ERR_HIP;
@@ -230,7 +238,7 @@ extern "C" int plx_scalar_ssfm_adaptive(double *ur, double *ui, const plx_ssfm_d
         while (zdone == 0) {
             int nc = 0;
             nrej = 0;
-            if (A.trial(zdone, dz, ltol, safety, nrej, nc)) { cleanup(); PLX_FAIL(PLX_ERR_HIP, "plx_scalar_ssfm_adaptive: HIP failure in adaptssfm"); }
+            if (int t = A.trial(zdone, dz, ltol, safety, nrej, nc)) return trial_failed(t);
             ncycle = nc;
         }
         if (dz > d.dzmaxt) dz = d.dzmaxt;

@@ -64,4 +64,9 @@ struct plx_ssfm {
     int64_t k_launches[4] = {0, 0, 0, 0};
 };
 
+// The linear step x = ifft(fft(x) .* exp(-i betat dz)) on one frame of `base`'s plan (lin_step, fiber.m:771-773) with the
+// step length forced from the launch: the three transform sweeps through the row-pass dispatch of the step loop and the
+// filter (ssfm_plan.hip).  The host-driven adaptive scheme (ssfm_gateway.hip) calls it; a failed launch is PLX_ERR_HIP.
+PLX_HIDDEN int plx_ssfm_linear_dev(plx_ssfm *P, const SsfmArgs &base, cplx *d_x, double dz, hipStream_t st);
+
 static const double kInv2Pi = 0.15915494309189533577;

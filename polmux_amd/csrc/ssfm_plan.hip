@@ -857,6 +857,21 @@ int plx_ssfm_filter_dev(plx_ssfm *P, cplx *d_ux, cplx *d_uy, const cplx *d_hmul,
     return PLX_OK;
 }
 
+int plx_ssfm_linear_dev(plx_ssfm *P, const SsfmArgs &base, cplx *d_x, double dz, hipStream_t st)
+{
+    SsfmArgs b = base;
+    b.ux = d_x; b.uy = nullptr; b.nframes = 1; b.hmul = nullptr; b.umat = nullptr;
+    b.force = 1; b.spm = 0; b.xpm = 0; b.f_cur = dz; b.f_leff = 0; b.f_sc = b.invN;
+    const unsigned FC = (unsigned)b.nfc;
+    const dim3 gcol((unsigned)((1 << b.p2) / b.W), FC);
+    launch(col_fwd_kernel(), gcol, dim3((unsigned)P->col_threads), P->lds_col, st, b);
+    launch_row(P, b, FC, st);
+    launch(col_inv_kernel(), gcol, dim3((unsigned)P->col_threads), P->lds_col, st, b);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) PLX_FAIL(PLX_ERR_HIP, std::string("linear step: launch failed: ") + hipGetErrorString(e));
+    return PLX_OK;
+}
+
 extern "C" int plx_ssfm_results(plx_ssfm *P, int nframes, double *firstdz, int32_t *ncycle)
 {
     if (!P || nframes < 1 || nframes > P->d.max_frames) PLX_FAIL(PLX_ERR_ARG, "plx_ssfm_results: bad argument");
