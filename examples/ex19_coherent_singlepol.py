@@ -14,7 +14,9 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
-def main(osnr=(3.0, 7.5), stop=(0.1, 68), max_runs=2000, seed=2, quiet=False):
+def main(osnr=(3.0, 7.5), stop=(0.1, 68), max_runs=2000, seed=2, quiet=False, linewidth=0.0):
+    """linewidth: the transmitter laser's linewidth normalised to the symbol rate, options.linewidth of ex19:121
+    (1E6 / symbrate / 1E9 there); 0 = a clean carrier."""
     import polmux_amd as px
     from polmux_amd import mc as pmc
     from polmux_amd import patterns, synth
@@ -45,7 +47,7 @@ def main(osnr=(3.0, 7.5), stop=(0.1, 68), max_runs=2000, seed=2, quiet=False):
         while cond and nruns < max_runs:
             px.reset_all(Nsymb, Nt, Nch)
             px.GSTATE.SYMBOLRATE = symbrate
-            E = px.lasersource(Pavg, lam, spac)
+            E = px.lasersource(Pavg, lam, spac, dict(linewidth=linewidth), rng=rng)   # ex19:121-123
             el_i = synth.electricsource_qpsk(patmat[:, 0], Nt, duty, roll)
             el_q = synth.electricsource_qpsk(patmat[:, 1], Nt, duty, roll)
             Eopt = synth.qi_modulator(E[:, 0], el_i, el_q)

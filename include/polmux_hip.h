@@ -375,6 +375,15 @@ int plx_decide_count_frames_dev(const double *d_sym, int64_t L, int32_t ncol, in
  * count above feeds ber_estimate.  d_sym [frame][ncol][L] complex; d_evm double [frame].                               */
 int plx_evm_dev(const double *d_sym, int64_t L, int32_t ncol, int nframes, double *d_evm, void *stream);
 
+/* The Monte-Carlo scripts' error count (ex20_coherent_polmux.m:155-173, ex19:141): samp2pat 'coherent' decisions
+ * (as plx_decide_count_dev), each column's (first, second) pairs differentially decoded as
+ * pat_decoder(patmat_hat, 'dqpsk', struct('binary', true)) (d_k = conj(s_k) s_{k-1}, circular, both patterns
+ * inverted), compared with d_pat_rx uint8 [ncol*2][L] = pat_decoder(pat, 'dqpsk') of the transmitted pattern (frame f:
+ * d_pat_rx + f * pat_frame_stride bytes, 0 = shared).  ncol 2: the received polarisations are exchanged iff
+ * errors(tx X vs rx Y) < errors(tx X vs rx X); d_err int64 [frame] = the errors of all 2*ncol bit streams.          */
+int plx_decide_count_dqpsk_dev(const double *d_sym, int64_t L, int32_t ncol, int nframes, const uint8_t *d_pat_rx,
+                               int64_t pat_frame_stride, int64_t *d_err, void *stream);
+
 /* ----------------------------------------------------------------- ampliflat --- */
 /* ampliflat(x,'gain',options), ampliflat.m:60-148 ("next" row): FIELD *= sqrt(gain) and
  * FIELD += sigma(c) * n with n complex Gaussian, E|Re n|^2 = E|Im n|^2 = 1.  sigma: host [nfc] (NULL/0 = no
@@ -384,6 +393,26 @@ int plx_evm_dev(const double *d_sym, int64_t L, int32_t ncol, int nframes, doubl
 int plx_ampliflat_dev(double *d_ux, double *d_uy, int64_t nfft, int32_t nfc, int nframes, double gain_lin,
                       const double *sigma, const double *d_noise, uint64_t seed, const int64_t *d_keys,
                       int32_t asex, int32_t asey, void *stream);
+
+/* --------------------------------------------------------------- laser phase noise --- */
+/* The Wiener phase of lasersource.m:182-192 (transmitter) and receiver_cohmix.m:206-216 (LO) per (frame, channel):
+ *   inc[0] = 0, inc[k] = sigma[c] * n[k] (k >= 1);  phi = cumsum(inc);  phi_b[k] = phi[k] - k/(nfft-1) * phi[nfft-1]
+ * with sigma = sqrt(2 pi linewidth / NT) (host, [nfc], finite, >= 0) and n[k] = sqrt(-2 ln u1) cos(2 pi u2), where
+ * (u1, u2) come from ONE Philox-4x32-10 call (r0..r3), u1 = (((uint64)r0 << 21) ^ (r1 >> 11)) + 0.5) / 2^53 and u2
+ * the same of (r2, r3), counter = (lo32(k), hi32(k), c, tag), key = (lo32(seed ^ K), hi32(seed) ^ hi32(K *
+ * 0x9E3779B97F4A7C15)), K = d_keys[frame] or the frame index.  tag: PLX_PHASE_TX or PLX_PHASE_LO; ampliflat's ASE
+ * uses 0 and 1 in that word, so no phase draw coincides with an ASE draw whatever the seeds.
+ * Frames are [frame][nfc][nfft].  d_phi_in: an injected phase of that shape used INSTEAD of the generator (the parity
+ * route).  Outputs (either or both):
+ *   d_ux [, d_uy]: u[(f nfc + c) pitch + j] *= exp(i sign phi[f][c][j stride]), j < nfft/stride (stride 1, pitch nfft:
+ *                  the transmitter field; stride NT/2 with the 2-sps receiver samples: the LO seen at the pick instants)
+ *   d_phi_out:     phi_b as [frame][nfc][nfft] float64 (generated route only)
+ * d_work: generated route, nframes * nfc * ceil(nfft / 2048) doubles.  nfft: power of two in [256, 2^20], nfc <= 64.  */
+#define PLX_PHASE_TX 2
+#define PLX_PHASE_LO 3
+int plx_phase_noise_dev(double *d_ux, double *d_uy, int64_t stride, int64_t pitch, double sign, int64_t nfft,
+                        int32_t nfc, int nframes, const double *sigma, uint64_t seed, const int64_t *d_keys,
+                        int32_t tag, const double *d_phi_in, double *d_phi_out, double *d_work, void *stream);
 
 /* ------------------------------------------------------------ coherent front end --- */
 /* The step between fiber() and CDE_OFDE(): receiver_cohmix.m:165-307 (optical filter x post-compensation,
@@ -414,6 +443,10 @@ int64_t plx_front_out_len(const plx_front *plan);   /* ceil(nfft / decim) */
  * d_out: [nframes][1 + dual_pol][out_len] complex128 RxSamples (RxPdmCohQpsk.m:63-72).                     */
 int plx_front_run_dev(plx_front *plan, double *d_ux, double *d_uy, int nframes, const int64_t *shift,
                       double *d_out, void *stream);
+/* the same with a per-frame LO phase: Elo[f][i] = Elo[i] * exp(i d_lophase[f][i]) (receiver_cohmix.m:223 with
+ * LO_PhaseNoise of frame f); d_lophase [nframes][nfft] float64 (NULL: plx_front_run_dev).                    */
+int plx_front_run_lo_dev(plx_front *plan, double *d_ux, double *d_uy, int nframes, const int64_t *shift,
+                         const double *d_lophase, double *d_out, void *stream);
 /* gateway tier (one frame, host arrays, MATLAB's separate planes; xi/yi may be NULL, yr NULL when !dual_pol):
  * out [out_len x (1 + dual_pol)] column-major = RxSamples; optional cur_r/cur_i [nfft x 2(1 + dual_pol)] = the
  * photocurrent columns [IricX IricY] of receiver_cohmix.m:300-307 (cur_i is filled with zeros).            */

@@ -19,6 +19,8 @@ PLX_ERR_REFERENCE = -4
 PLX_ERR_TIMEOUT = -5
 PLX_SSFM_SHARE_DEVICE = 1
 PLX_DBP_STREAMED = 1
+PLX_PHASE_TX = 2
+PLX_PHASE_LO = 3
 
 
 class PolmuxError(RuntimeError):
@@ -126,11 +128,15 @@ SIGNATURES = {
     "plx_decide_count_dev": [_vp, _i64, _i32, C.c_int, _vp, _vp, _vp, _vp],
     "plx_decide_count_frames_dev": [_vp, _i64, _i32, C.c_int, _vp, _i64, _vp, _vp, _vp],
     "plx_evm_dev": [_vp, _i64, _i32, C.c_int, _vp, _vp],
+    "plx_decide_count_dqpsk_dev": [_vp, _i64, _i32, C.c_int, _vp, _i64, _vp, _vp],
     "plx_ampliflat_dev": [_vp, _vp, _i64, _i32, C.c_int, _dbl, _vp, _vp, C.c_uint64, _vp, _i32, _i32, _vp],
+    "plx_phase_noise_dev": [_vp, _vp, _i64, _i64, _dbl, _i64, _i32, C.c_int, _vp, C.c_uint64, _vp, _i32, _vp, _vp, _vp,
+                            _vp],
     "plx_front_create": [C.POINTER(_vp), C.POINTER(FrontDesc)],
     "plx_front_destroy": [_vp],
     "plx_front_out_len": [_vp],
     "plx_front_run_dev": [_vp, _vp, _vp, C.c_int, _vp, _vp, _vp],
+    "plx_front_run_lo_dev": [_vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp],
     "plx_rx_front": [_vp, _vp, _vp, _vp, C.POINTER(FrontDesc), _vp, _vp, _vp, _vp, _vp],
     "plx_filter_create": [C.POINTER(_vp), _i64, C.c_int, _vp, _vp],
     "plx_filter_destroy": [_vp],

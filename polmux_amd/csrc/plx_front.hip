@@ -25,6 +25,7 @@ namespace {
 struct FrontArgs {
     cplx *ux, *uy;
     const cplx *elo;      // [n] or null
+    const double *lophase;   // [frame][n] LO phase noise or null
     double elo_s;
     int64_t n;
     int balanced, dual;
@@ -46,7 +47,8 @@ __global__ __launch_bounds__(256) void k_mix(FrontArgs a)
 {
     const size_t base = (size_t)blockIdx.y * a.n;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += (int64_t)gridDim.x * blockDim.x) {
-        const cplx lo = a.elo ? a.elo[i] : make_double2(a.elo_s, 0.0);
+        cplx lo = a.elo ? a.elo[i] : make_double2(a.elo_s, 0.0);
+        if (a.lophase) lo = cmul(lo, cexpi(a.lophase[base + i]));       // Elo = LO_Ecw fastexp(LO_PhaseNoise), :223
         a.ux[base + i] = hybrid(a.ux[base + i], lo, a.balanced);
         if (a.dual) a.uy[base + i] = hybrid(a.uy[base + i], lo, a.balanced);
     }
@@ -215,8 +217,8 @@ extern "C" int plx_front_destroy(plx_front *P)
 
 extern "C" int64_t plx_front_out_len(const plx_front *P) { return P ? P->nout : 0; }
 
-extern "C" int plx_front_run_dev(plx_front *P, double *d_ux, double *d_uy, int nframes, const int64_t *shift,
-                                 double *d_out, void *stream)
+extern "C" int plx_front_run_lo_dev(plx_front *P, double *d_ux, double *d_uy, int nframes, const int64_t *shift,
+                                    const double *d_lophase, double *d_out, void *stream)
 {
     if (!P || !d_ux || !d_out) PLX_FAIL(PLX_ERR_ARG, "plx_front_run_dev: null argument");
     if (nframes < 1 || nframes > P->d.max_frames) PLX_FAIL(PLX_ERR_ARG, "plx_front_run_dev: nframes outside [1, max_frames]");
@@ -227,7 +229,7 @@ extern "C" int plx_front_run_dev(plx_front *P, double *d_ux, double *d_uy, int n
     int rc = plx_ssfm_filter_dev(P->fft, (cplx *)d_ux, (cplx *)d_uy, P->d_hopt, nframes, stream);   // :183, :232-233
     if (rc != PLX_OK) return rc;
     FrontArgs a;
-    a.ux = (cplx *)d_ux; a.uy = (cplx *)d_uy; a.elo = P->d_elo; a.elo_s = P->d.elo_scalar; a.n = N;
+    a.ux = (cplx *)d_ux; a.uy = (cplx *)d_uy; a.elo = P->d_elo; a.lophase = d_lophase; a.elo_s = P->d.elo_scalar; a.n = N;
     a.balanced = P->d.balanced; a.dual = dual;
     unsigned gx = (unsigned)((N + 255) / 256);
     if (gx > 256) gx = 256;
@@ -249,6 +251,12 @@ extern "C" int plx_front_run_dev(plx_front *P, double *d_ux, double *d_uy, int n
     PLX_LAUNCH(k_decimate, dim3((unsigned)((P->nout + 255) / 256), (unsigned)nframes, (unsigned)(dual + 1)), dim3(256), 0, st, g);
     PLX_HIP(hipGetLastError());
     return PLX_OK;
+}
+
+extern "C" int plx_front_run_dev(plx_front *P, double *d_ux, double *d_uy, int nframes, const int64_t *shift,
+                                 double *d_out, void *stream)
+{
+    return plx_front_run_lo_dev(P, d_ux, d_uy, nframes, shift, nullptr, d_out, stream);
 }
 
 // ---------------------------------------------------------------- generic spectral filter ---

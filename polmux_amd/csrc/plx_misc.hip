@@ -2,6 +2,7 @@
 #include "../../include/polmux_hip.h"
 #include "plx_common.h"
 #include "plx_gateway.h"
+#include "plx_philox.h"
 
 #include <cstring>
 
@@ -44,22 +45,9 @@ __global__ __launch_bounds__(256) void k_pick(const cplx *__restrict__ in, cplx 
         out[(size_t)sig * out_pitch + i] = cscale(in[(size_t)sig * n_in + offset + i * stride], scale);
 }
 // ---- ampliflat.m:78-148 : flat gain + ASE (the step between spans) -------------------
-// Philox-4x32-10 (Salmon et al., SC'11), counter = (sample, column, polarisation, 0), key = (seed, frame
-// key): one call -> one complex normal sample by Box-Muller.  Counter-based, so the noise of a realisation
-// depends only on its key, never on how frames are batched or sharded over GPUs.
-__device__ __forceinline__ void philox4x32(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
-                                           uint32_t *out)
-{
-    for (int r = 0; r < 10; r++) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n1 = (uint32_t)p1;
-        const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1, n3 = (uint32_t)p0;
-        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-
+// Philox-4x32-10 (plx_philox.h), counter = (sample lo, sample hi, column, polarisation), key = (seed, frame key): one call ->
+// one complex normal sample by Box-Muller.  Counter-based, so the noise of a realisation depends only on its key,
+// never on how frames are batched or sharded over GPUs.
 struct AmpArgs {
     cplx *ux, *uy;          // [frame][nfc][nfft]
     const cplx *noise;      // optional injected unit noise [frame][2*nfc][nfft] ([X cols | Y cols], ampliflat.m:123-129)

@@ -771,6 +771,60 @@ __global__ __launch_bounds__(256) void k_decide(const cplx *sym, int64_t L, int 
     }
 }
 
+// Differential decoding + error count of the Monte-Carlo scripts (ex20_coherent_polmux.m:155-173).  A decided
+// symbol is the star i^q of pat2stars(binary): (0,0) -> 1 (q 0), (0,1) -> i (1), (1,1) -> -1 (2), (1,0) -> -i (3);
+// d_k = conj(s_k) s_{k-1} = i^(q_{k-1} - q_k) (fastshift(st,1): circular), and stars2pat + inversion (pat_decoder.m:
+// 68-72) map d = i^m to (1,1), (1,0), (0,0), (0,1) for m = 0..3.  cnt[t][r]: errors of tx polarisation t against rx
+// polarisation r; one workgroup per frame.
+__device__ __forceinline__ int star_q(cplx v)
+{
+    const double ph = atan2(v.y, v.x);
+    const int first = fabs(ph) <= 1.57079632679489661923 ? 1 : 0, second = ph > 0 ? 1 : 0;
+    return first ? (second ? 2 : 3) : (second ? 1 : 0);   // the bits of k_decide -> q
+}
+
+__global__ __launch_bounds__(256) void k_decide_dqpsk(const cplx *sym, int64_t L, int ncol, const uint8_t *pat, size_t pstride,
+                                                      unsigned long long *err)
+{
+    PLX_DYN_LDS(lds);
+    unsigned long long *red = (unsigned long long *)lds;
+    const int tid = threadIdx.x, nthr = blockDim.x;
+    const size_t f = blockIdx.x;
+    pat += f * pstride;
+    unsigned long long cnt[2][2] = {{0, 0}, {0, 0}};
+    for (int64_t i = tid; i < L; i += nthr) {
+        const int64_t ip = i ? i - 1 : L - 1;
+        int d0[2], d1[2];
+        for (int r = 0; r < ncol; r++) {
+            const cplx *s = sym + (f * ncol + r) * (size_t)L;
+            const int m = (star_q(s[ip]) - star_q(s[i])) & 3;
+            d0[r] = m < 2 ? 1 : 0;              // inverted first bit: m 0,1 -> 1; 2,3 -> 0
+            d1[r] = (m == 0 || m == 3) ? 1 : 0; // inverted second bit: m 0,3 -> 1; 1,2 -> 0
+        }
+        for (int t = 0; t < ncol; t++) {
+            const uint8_t p0 = pat[(size_t)(2 * t) * L + i], p1 = pat[(size_t)(2 * t + 1) * L + i];
+            for (int r = 0; r < ncol; r++) cnt[t][r] += (unsigned long long)((p0 != d0[r]) + (p1 != d1[r]));
+        }
+    }
+    for (int t = 0; t < 2; t++)
+        for (int r = 0; r < 2; r++) {
+            unsigned long long v = cnt[t][r];
+            for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+            cnt[t][r] = v;
+        }
+    if ((tid & 63) == 0)
+        for (int j = 0; j < 4; j++) red[4 * (tid >> 6) + j] = cnt[j >> 1][j & 1];
+    __syncthreads();
+    if (tid == 0) {
+        unsigned long long e[4] = {0, 0, 0, 0};
+        for (int w = 0; w < (nthr + 63) / 64; w++)
+            for (int j = 0; j < 4; j++) e[j] += red[4 * w + j];
+        // e[0] = tx X vs rx X, e[1] = tx X vs rx Y, e[2] = tx Y vs rx X, e[3] = tx Y vs rx Y
+        const bool swap = ncol == 2 && e[1] < e[0];
+        err[f] = ncol == 1 ? e[0] : (swap ? e[1] + e[2] : e[0] + e[3]);
+    }
+}
+
 // Per-frame error-vector magnitude of the recovered symbols: mean over the frame's symbols (all columns) of
 // |s - s_hat|^2, s_hat the unit-modulus QPSK point of the quadrant samp2pat decides (samp2pat.m:61-66).  A continuous
 // per-realisation sample for mc_estimate (mc_estimate.m:133-212) beside the integer error count of ber_estimate.
@@ -1290,6 +1344,17 @@ extern "C" int plx_decide_count_frames_dev(const double *d_sym, int64_t L, int32
     if (!d_sym || L < 1 || ncol < 1 || nframes < 1 || pat_frame_stride < 0) PLX_FAIL(PLX_ERR_ARG, "plx_decide_count_dev: bad argument");
     PLX_LAUNCH(k_decide, dim3((unsigned)(nframes * ncol)), dim3(256), 16 * sizeof(unsigned long long), stream,
                (const cplx *)d_sym, L, (int)ncol, d_pat, (size_t)pat_frame_stride, d_pat_hat, (unsigned long long *)d_err);
+    PLX_HIP(hipGetLastError());
+    return PLX_OK;
+}
+
+extern "C" int plx_decide_count_dqpsk_dev(const double *d_sym, int64_t L, int32_t ncol, int nframes, const uint8_t *d_pat_rx,
+                                          int64_t pat_frame_stride, int64_t *d_err, void *stream)
+{
+    if (!d_sym || !d_pat_rx || !d_err || L < 1 || ncol < 1 || ncol > 2 || nframes < 1 || pat_frame_stride < 0)
+        PLX_FAIL(PLX_ERR_ARG, "plx_decide_count_dqpsk_dev: bad argument");
+    PLX_LAUNCH(k_decide_dqpsk, dim3((unsigned)nframes), dim3(256), 16 * sizeof(unsigned long long), stream,
+               (const cplx *)d_sym, L, (int)ncol, d_pat_rx, (size_t)pat_frame_stride, (unsigned long long *)d_err);
     PLX_HIP(hipGetLastError());
     return PLX_OK;
 }

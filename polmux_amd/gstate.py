@@ -170,9 +170,31 @@ def unique_field_shifts():
     return (np.sign(v) * np.floor(np.abs(v) + 0.5)).astype(np.int64)                # MATLAB round
 
 
-def lasersource(Ptx, lam, spac=None):
-    """GSTATE.LAMBDA / GSTATE.POWER bookkeeping of lasersource.m:150-178; returns the CW carriers."""
+def lasersource(Ptx, lam, spac=None, options=None, rng=None):
+    """lasersource.m:65-195: GSTATE.LAMBDA / GSTATE.POWER bookkeeping (:150-178) and the CW carriers [nfft x nch],
+    with options.linewidth (normalised to the symbol rate, scalar or per channel: Wiener phase noise with a Brownian
+    bridge, :182-192; randn -> rng, a numpy Generator) or options.pnoise (a given phase, :193-194).  For nch > 1 the
+    reference text is followed literally: freq_noise(1) = 0 zeroes the first sample of column 1 only, and the bridge
+    loop runs over column 1 with phase_noise(end), the last sample of the LAST column; other columns are not bridged.
+    n0, anoise and single are not supported (they raise)."""
     nch = GSTATE.NCH
+    linewidth, pnoise = 0.0, None
+    if options is not None:
+        known = ("n0", "linewidth", "anoise", "pnoise", "single")
+        for k in options:                                               # checkfields(options, {...}), :74
+            if k.lower() not in known:
+                raise ValueError("the field %s of options does not exist" % k)
+        opt = {k.lower(): v for k, v in options.items()}
+        for k in ("n0", "anoise", "single"):
+            if k in opt:
+                raise ValueError("lasersource: options.%s is not supported" % k)
+        linewidth = opt.get("linewidth", 0.0)
+        pnoise = opt.get("pnoise")
+    linewidth = np.atleast_1d(np.asarray(linewidth, dtype=float)).reshape(-1)
+    if linewidth.size == 1 and nch > 1:                                 # :124-129
+        linewidth = np.full(nch, linewidth[0])
+    elif linewidth.size != nch:
+        raise ValueError("linewidth length must be 1 or Nch")
     Pin = np.full(nch, float(Ptx)) if np.size(Ptx) == 1 else np.asarray(Ptx, dtype=float)
     if np.size(lam) == 1 and nch > 1:
         if spac is None:
@@ -184,4 +206,19 @@ def lasersource(Ptx, lam, spac=None):
             raise ValueError("wrong length for LAM (must be 1 or # channels)")
     GSTATE.LAMBDA = lamt
     GSTATE.POWER = Pin
-    return np.ones((GSTATE.NSYMB * GSTATE.NT, 1)) * np.sqrt(Pin)
+    nfft = GSTATE.NSYMB * GSTATE.NT
+    E = np.ones((nfft, 1)) * np.sqrt(Pin)
+    if np.all(linewidth != 0):                                          # `if linewidth`: every element nonzero
+        rng = rng if rng is not None else np.random.default_rng()
+        freq_noise = np.sqrt(2 * np.pi * linewidth / GSTATE.NT)[None, :] * rng.standard_normal((nfft, nch))
+        freq_noise[0, 0] = 0.0                                          # freq_noise(1) = 0
+        phase_noise = np.cumsum(freq_noise, axis=0)
+        last = phase_noise[-1, -1]                                      # phase_noise(end)
+        n = max(phase_noise.shape)                                      # length(phase_noise)
+        col = phase_noise.reshape(-1, order="F")                        # linear indexing: column 1 for nnoise <= nfft
+        col[:n] -= np.arange(n) / (n - 1) * last                       # phase_noise(end) is read before it changes
+        phase_noise = col.reshape(phase_noise.shape, order="F")
+        E = E * np.exp(1j * phase_noise)
+    elif pnoise is not None:
+        E = E * np.exp(1j * np.asarray(pnoise, dtype=float).reshape(nfft, -1))
+    return E

@@ -19,6 +19,17 @@ from .gstate import GSTATE
 from .rx import cde_transfer, dsp_params_struct
 
 
+def dqpsk_expected(bits):
+    """[4, nsymb] uint8: pat_decoder(pat, 'dqpsk') of the quaternary X and Y patterns behind bits [nsymb x 4] (the
+    de Bruijn (first, second) pairs of synth.pdm_qpsk_field, pat = 2 first + second), ex20_coherent_polmux.m:124-125"""
+    from . import patterns
+    out = []
+    for c in (0, 2):
+        _, pm = patterns.pat_decoder(2 * bits[:, c].astype(int) + bits[:, c + 1].astype(int), "dqpsk")
+        out += [pm[:, 0], pm[:, 1]]
+    return np.ascontiguousarray(np.stack(out).astype(np.uint8))
+
+
 def _u01(keys):
     """splitmix64 finaliser of uint64 keys -> doubles in [0, 1) (53 bits)."""
     with np.errstate(over="ignore"):
@@ -38,7 +49,7 @@ class HotPathConfig:
                  polmethod="cma", cma_taps=7, cma_mu=1 / 6000, freqavg=500, phasavg=3, poworder=2,
                  frontend="pick", oftype="gauss", obw=1.9, oord=3, eftype="bessel5", ebw=0.65, eord=4, lopower=0.0,
                  adcbits=5, span_nf_db=None, rx_amp=False, variants=1, nch=1, chspacing=0.4, share_device=False,
-                 equaliser="cde", dbp_steps=4, dbp_xi=1.0):
+                 equaliser="cde", dbp_steps=4, dbp_xi=1.0, tx_linewidth=0.0, lo_linewidth=0.0, decoding="rotation"):
         """frontend: 'pick' = 2-sps sampling supplied by the harness; 'cohmix' = the reference's own
         receiver_cohmix + ADC + decimate chain (RxPdmCohQpsk.m, Run_my_PDM_QPSK.m:52-73 defaults) on the device.
         nspans > 1: every span but the last is followed by an in-line flat amplifier restoring its loss
@@ -58,7 +69,15 @@ class HotPathConfig:
         equaliser: 'cde' = CDE_OFDE (overlap-save dispersion compensation); 'dbp' = digital backpropagation of the nspans
         spans on the 2-sps samples (polmux_amd.dbp, plx_dbp_apply_dev) with dbp_steps uniform steps per span and dbp_xi
         of the nonlinearity, using the reference wavelength's D, S and gamma (WDM channel-frames as well); 'pick' front
-        end only (the cohmix LO/ADC chain is not proportional to the field)."""
+        end only (the cohmix LO/ADC chain is not proportional to the field).
+        tx_linewidth, lo_linewidth: laser linewidths normalised to the symbol rate (lasersource.m options.linewidth,
+        receiver_cohmix.m x.lolinewidth): every realisation gets its own Wiener phase per laser, drawn on the device
+        (plx_phase_noise_dev) and keyed by the realisation keys; one transmitter laser per channel feeds both
+        polarisations, and the LO of a channel's receiver multiplies the hybrid's LO field (cohmix) or acts as exp(-i phi)
+        on the picked 2-sps samples (pick).  0: no phase noise, nothing is launched.
+        decoding: 'rotation' = errors_resolved's minimum over the pi/2 rotations and the polarisation swap; 'dqpsk' = the
+        Monte-Carlo scripts' differential decoding of both patterns plus ex20's swap rule (errors_dqpsk); McCampaign counts
+        with it."""
         self.__dict__.update(locals())
         del self.__dict__["self"]
 
@@ -74,6 +93,12 @@ class HotPath:
             raise ValueError("equaliser must be 'cde' or 'dbp'")
         if cfg.equaliser == "dbp" and cfg.frontend != "pick":
             raise ValueError("equaliser='dbp' needs frontend='pick' (the cohmix LO/ADC chain is not proportional to the field)")
+        for name in ("tx_linewidth", "lo_linewidth"):
+            v = getattr(cfg, name)
+            if not (np.ndim(v) == 0 and math.isfinite(float(v)) and float(v) >= 0):
+                raise ValueError("%s must be a finite scalar >= 0 (normalised to the symbol rate)" % name)
+        if cfg.decoding not in ("rotation", "dqpsk"):
+            raise ValueError("decoding must be 'rotation' or 'dqpsk'")
         self.torch = torch
         self.cfg = cfg
         self.F = int(max_frames)
@@ -129,6 +154,13 @@ class HotPath:
             self.tx_var = torch.from_numpy(np.stack([np.stack([v[0], v[1]]) for v in self.var_host])).to(self.dev)   # [V, 2, n]
             pv = np.stack([np.ascontiguousarray(v[2].T.astype(np.uint8)) for v in self.var_host])               # [V, 4, nsymb]
             self.pat_frames = torch.from_numpy(pv[np.arange(self.CF) % self.nvar].copy()).to(self.dev)         # [F nch, 4, nsymb]
+        # pat_decoder(pat, 'dqpsk') of each variant's transmitted X and Y patterns (ex20_coherent_polmux.m:124-125)
+        dv = np.stack([dqpsk_expected(v[2]) for v in self.var_host])                                          # [V, 4, nsymb]
+        self.dpat = torch.from_numpy(dv[0]).to(self.dev)
+        if self.nvar > 1:
+            self.dpat_frames = torch.from_numpy(dv[np.arange(self.CF) % self.nvar].copy()).to(self.dev)
+        self._phase_work = {}                            # tile sums of the phase generator, per laser (allocated on use)
+        self._lo_buf = None                              # [F nch, nfft] LO phase of the cohmix route (allocated on use)
         self.rx_gain = None                              # per-frame receiver scale of a launch-power ladder (make_batch)
         # --- Rx plans ---
         self.Lrx = 2 * cfg.nsymb
@@ -244,14 +276,19 @@ class HotPath:
     def stream(self):
         return self.torch.cuda.current_stream().cuda_stream
 
-    def fibre(self, ux, uy, span_keys=None, inject_noise=None):
+    def fibre(self, ux, uy, span_keys=None, inject_noise=None, tx_phase=None):
         """ux, uy: [F, n] (or [F, nch, n]) complex128 device tensors ([frame][channel][nfft]), propagated in place.
         span_keys: per-frame keys of the amplifiers' ASE streams (realisation indices).  inject_noise: optional list,
         one entry per amplifier, of [F, 2, n] complex128 device tensors used INSTEAD of the device generator
-        (ampliflat's options.noise, ampliflat.m:123-129: the parity route)."""
+        (ampliflat's options.noise, ampliflat.m:123-129: the parity route).
+        tx_phase: optional [F, nch, n] float64 device tensor, the transmitter lasers' phase used INSTEAD of the
+        cfg.tx_linewidth generator (keyed by span_keys, or the frame index): both polarisations *= exp(+i phi)."""
         F = ux.shape[0]
         self._rows = self._steps = 0
         cfg = self.cfg
+        if tx_phase is not None or cfg.tx_linewidth > 0:      # lasersource.m:182-192: one laser feeds X and Y
+            self._phase(ux.data_ptr(), uy.data_ptr(), 1, cfg.nfft, 1.0, F, span_keys, _abi.PLX_PHASE_TX, cfg.tx_linewidth,
+                        tx_phase)
         namp = 0
         for span in range(cfg.nspans):
             self.lib.call("plx_ssfm_propagate_dev", self.ssfm, ux.data_ptr(), uy.data_ptr(), F, self.stream())
@@ -275,13 +312,54 @@ class HotPath:
                               kt.data_ptr() if kt is not None else None, 1, 1, self.stream())
                 namp += 1
 
-    def receive(self, ux, uy, noise_sigma=0.0, noise_seed=None, side_stream=None, noise_keys=None):
+    def _phase(self, pu, pv, stride, pitch, sign, F, keys, tag, linewidth, phi_in, phi_out=None):
+        """one plx_phase_noise_dev call on F frames of nch channels: the injected phi_in, or the generator keyed by keys"""
+        torch = self.torch
+        n, nch = self.cfg.nfft, self.nch
+        if phi_in is not None:
+            self._phase_shape(phi_in, F)
+            self.lib.call("plx_phase_noise_dev", pu, pv, stride, pitch, sign, n, nch, F, None, 0, None, tag,
+                          phi_in.data_ptr(), None, None, self.stream())
+            return
+        need = self.F * nch * (-(-n // 2048))
+        work = self._phase_work.get(tag)        # one per laser: the LO's may run on the receiver's stream beside the Tx's
+        if work is None:
+            work = self._phase_work[tag] = torch.empty(need, dtype=torch.float64, device=self.dev)
+        sig = np.full(nch, math.sqrt(2 * math.pi * float(linewidth) / self.cfg.nt))
+        kt = None
+        if keys is not None:
+            kt = torch.as_tensor(np.asarray(list(keys), dtype=np.int64), device=self.dev)
+        self.lib.call("plx_phase_noise_dev", pu, pv, stride, pitch, sign, n, nch, F, sig.ctypes.data, 20260101,
+                      kt.data_ptr() if kt is not None else None, tag, None, phi_out, work.data_ptr(), self.stream())
+
+    def _phase_shape(self, phi, F):
+        n = self.cfg.nfft
+        if tuple(phi.shape) != (F, self.nch, n) or phi.dtype != self.torch.float64 or not phi.is_contiguous():
+            raise ValueError("an injected phase must be a contiguous float64 tensor [F, nch, nfft] = [%d, %d, %d]" % (F, self.nch, n))
+
+    def errors_dqpsk(self, F):
+        """Per-frame bit errors as the Monte-Carlo scripts count them (ex20_coherent_polmux.m:155-173): decisions of the
+        symbols now in self.sym, differentially decoded and compared with pat_decoder(pat, 'dqpsk') of the transmitted
+        patterns after ex20's polarisation-swap rule.  One device call; returns an int64 tensor [F]."""
+        out = self.torch.empty(F, dtype=self.torch.int64, device=self.dev)
+        pat, stride = (self.dpat_frames, 4 * self.cfg.nsymb) if self.nvar > 1 else (self.dpat, 0)
+        self.lib.call("plx_decide_count_dqpsk_dev", self.sym.data_ptr(), self.cfg.nsymb, 2, F, pat.data_ptr(), stride,
+                      out.data_ptr(), self.stream())
+        return out
+
+    def errors(self, F):
+        """per-frame errors by cfg.decoding: errors_resolved ('rotation') or errors_dqpsk ('dqpsk')"""
+        return self.errors_dqpsk(F) if self.cfg.decoding == "dqpsk" else self.errors_resolved(F)
+
+    def receive(self, ux, uy, noise_sigma=0.0, noise_seed=None, side_stream=None, noise_keys=None, lo_phase=None):
         """Front end (2-sps pick, or receiver_cohmix + ADC + decimate), CDE, DSP, decisions.  Returns err [F,2] (device).
         Receiver noise (sigma per quadrature on the 2-sps samples, an ASE stand-in) comes from the device Philox
         generator of plx_ampliflat_dev keyed by (noise_seed, noise_keys[frame] or frame): with noise_keys = the
         realisation indices the noise of a realisation does not depend on batching or sharding.
         With side_stream the whole receiver is enqueued on that stream behind the fibre of this batch, so
-        the latency-bound CMA recurrence overlaps the HBM-bound fibre sweeps of the NEXT batch."""
+        the latency-bound CMA recurrence overlaps the HBM-bound fibre sweeps of the NEXT batch.
+        lo_phase: optional [F, nch, n] float64 device tensor, the LO phase of each channel's receiver used INSTEAD of the
+        cfg.lo_linewidth generator (keyed by noise_keys, or the frame index)."""
         if side_stream is not None and not self.overlap_ok():
             side_stream = None
         if side_stream is not None:
@@ -290,7 +368,7 @@ class HotPath:
             ready.record(torch.cuda.current_stream())
             side_stream.wait_event(ready)
             with torch.cuda.stream(side_stream):
-                return self.receive(ux, uy, noise_sigma, noise_seed, None, noise_keys)
+                return self.receive(ux, uy, noise_sigma, noise_seed, None, noise_keys, lo_phase)
         F = ux.shape[0] * self.nch             # channel-frames: every channel of a 'sepfields' frame has its own receiver
         cfg = self.cfg
         half = cfg.nt // 2
@@ -298,15 +376,30 @@ class HotPath:
         rx = self.rx[:F]
         if self.nch > 1:
             ux, uy = ux.view(F, cfg.nfft), uy.view(F, cfg.nfft)
+        Ff = F // self.nch                     # frames (the phase tensors are [Ff, nch, nfft])
+        lo = lo_phase is not None or cfg.lo_linewidth > 0
         if self.front is not None:             # receiver_cohmix + ADC + decimate; ux, uy are consumed
             if self.rx_gain is not None:       # launch-power ladder: each frame normalised by its own power
                 ux.mul_(self.rx_gain[:F, :, 0])
                 uy.mul_(self.rx_gain[:F, :, 0])
-            self.front.run(ux, uy, self.front_shifts, out=rx)
+            lop = None
+            if lo_phase is not None:
+                self._phase_shape(lo_phase, Ff)
+                lop = lo_phase
+            elif lo:                           # Elo[f] = Elo exp(i phi_b[f]) (receiver_cohmix.m:223): phi_b of every channel-frame
+                if self._lo_buf is None:
+                    self._lo_buf = self.torch.empty((self.CF, cfg.nfft), dtype=self.torch.float64, device=self.dev)
+                lop = self._lo_buf
+                self._phase(None, None, 1, cfg.nfft, 1.0, Ff, noise_keys, _abi.PLX_PHASE_LO, cfg.lo_linewidth, None,
+                            lop.data_ptr())
+            self.front.run(ux, uy, self.front_shifts, out=rx, lo_phase=lop)
         else:
             for pol, src in enumerate((ux, uy)):   # rx[f][pol][i] = scale * u_pol[f][i*half]
                 self.lib.call("plx_pick_dev", src.data_ptr(), rx.data_ptr() + pol * self.Lrx * 16, cfg.nfft, self.Lrx, 0,
                               half, self.rx_scale, F, 2 * self.Lrx, st)
+            if lo:                             # the LO at the pick instants: rx[f][pol][i] *= exp(-i phi_b[f][i half])
+                self._phase(rx.data_ptr(), rx.data_ptr() + self.Lrx * 16, half, 2 * self.Lrx, -1.0, Ff, noise_keys,
+                            _abi.PLX_PHASE_LO, cfg.lo_linewidth, lo_phase)
         if self.rx_gain is not None and self.front is None:   # launch-power ladder: each frame normalised by its own power
             rx.mul_(self.rx_gain[:F])
         if noise_sigma:
@@ -518,7 +611,7 @@ class McCampaign:
             hp.receive(ux, uy, self.sigma, 20260101, side, idx)   # receiver noise keyed by realisation index
             with torch.cuda.stream(rxs):
                 v = hp.evm(n)              # a continuous per-realisation sample (mc_estimate) beside the error count
-                e = hp.errors_resolved(n)
+                e = hp.errors(n)
                 if side is not None:
                     ux.record_stream(rxs); uy.record_stream(rxs)
                 done = torch.cuda.Event()

@@ -204,16 +204,23 @@ class _Front:
         self.nout = int(self.lib.lib.plx_front_out_len(self.plan))
         self.dual, self.nfft = bool(dual), nfft
 
-    def run(self, ux, uy, shifts=None, out=None):
-        """ux, uy: torch complex128 [F, nfft] (overwritten with the photocurrents I + jQ); returns [F, npol, nout]."""
+    def run(self, ux, uy, shifts=None, out=None, lo_phase=None):
+        """ux, uy: torch complex128 [F, nfft] (overwritten with the photocurrents I + jQ); returns [F, npol, nout].
+        lo_phase: optional float64 device tensor holding [F][nfft], the LO phase noise of each frame (plx_front_run_lo_dev)."""
         import torch
         F = ux.shape[0]
         npol = 2 if self.dual else 1
         if out is None:
             out = torch.empty((F, npol, self.nout), dtype=torch.complex128, device=ux.device)
         sh = (C.c_int64 * 2)(*(list(shifts) + [0, 0])[:2]) if shifts is not None else None
-        self.lib.call("plx_front_run_dev", self.plan, ux.data_ptr(), uy.data_ptr() if self.dual else None, F, sh,
-                      out.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        if lo_phase is not None:
+            if lo_phase.dtype != torch.float64 or not lo_phase.is_contiguous() or lo_phase.numel() < F * self.nfft:
+                raise ValueError("lo_phase must be a contiguous float64 tensor holding [F][nfft]")
+            self.lib.call("plx_front_run_lo_dev", self.plan, ux.data_ptr(), uy.data_ptr() if self.dual else None, F, sh,
+                          lo_phase.data_ptr(), out.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        else:
+            self.lib.call("plx_front_run_dev", self.plan, ux.data_ptr(), uy.data_ptr() if self.dual else None, F, sh,
+                          out.data_ptr(), torch.cuda.current_stream().cuda_stream)
         return out
 
     def close(self):
