@@ -98,6 +98,13 @@ int plx_ssfm_create(plx_ssfm **plan, const plx_ssfm_desc *desc);
  * another one): for processes that share a GPU, and for plans that propagate beside a long-running kernel of another
  * stream (a one-team plan -- plx_ssfm_info: info[4] == info[3] -- whose receiver runs beside the next batch's fibre). */
 #define PLX_SSFM_SHARE_DEVICE 1u
+/* PLX_SSFM_XPM_MANAKOV -- cross-phase modulation between the channels of a dual-polarisation 'sepfields' plan in the
+ * Manakov form (the reference stops at fiber.m:854): a descriptor with dual_pol, fls[3] = 1,
+ * nfc > 1 and manakov = 1 is accepted and every channel k takes, per time sample and from the fields at the start of the
+ * step,  u_k <- exp(-i g_k Leff [ s P_k I + x sum_{j != k} (P_j I + u_j u_j^H) ]) u_k  (s = fls[2], x = fls[3]).  Such a
+ * plan takes the three-sweep step (plx_ssfm_info: info[0] == 0).  With manakov = 0 the reference's error stays
+ * (PLX_ERR_REFERENCE); with nfc == 1, fls[3] == 0 or a scalar plan the flag changes nothing.                          */
+#define PLX_SSFM_XPM_MANAKOV 2u
 int plx_ssfm_create_ex(plx_ssfm **plan, const plx_ssfm_desc *desc, uint32_t flags);
 /* Plan-time tuning: which kernels and which split a plan takes where the library has more than one (the tests compare
  * each kernel with the one it replaced; A/B measurements).  NOT read from the environment: a plan created without a

@@ -18,6 +18,7 @@ PLX_ERR_UNSUPPORTED = -3
 PLX_ERR_REFERENCE = -4
 PLX_ERR_TIMEOUT = -5
 PLX_SSFM_SHARE_DEVICE = 1
+PLX_SSFM_XPM_MANAKOV = 2
 PLX_DBP_STREAMED = 1
 PLX_PHASE_TX = 2
 PLX_PHASE_LO = 3

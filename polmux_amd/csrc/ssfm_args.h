@@ -48,7 +48,11 @@ struct SsfmArgs {
     cplx *e1tab, *e2tab;
     double d1slope;                // D: db1 in turns per unit of m
     int tmax;                      // trunks the tables hold per frame
-    double *psum;                  // [F][N] row-sum of channel powers (scalar XPM, :795)
+    union {                        // one plan-owned buffer, by the kind of plan (the argument block keeps its layout)
+        double *psum;              // scalar XPM: [F][N] row-sum of channel powers (:795, k_rowsum)
+        cplx *stokes;              // Manakov XPM between dual-polarisation channels: [F][N][2] the channels' coherency sums
+                                   // {(Axx, Ayy), (Re Axy, Im Axy)} per sample, 32 B (k_stokes_sum)
+    };
     FrameCtl *ctl;
     unsigned long long *umax;      // [F][nfc] bit pattern of max |u|^2 (>= 0)
     int *ndone;                    // [0] frames that have reached the fibre end, [1] sticky abort word (a frame barrier timed out)

@@ -1,5 +1,6 @@
 // ssfm_col.hip -- the plain column sweeps of the three-sweep step: k_col_fwd (Kerr step fused on load + N1-point DIF) and
-// k_col_inv (N1-point DIT + attenuation + nextstep's maximum).  fiber.m:776-874, :531-532, :694-696.
+// k_col_inv (N1-point DIT + attenuation + nextstep's maximum).  fiber.m:776-874, :531-532, :694-696.  k_col_fwd_xpm is k_col_fwd
+// with the Manakov cross-phase modulation between the channels of a dual-polarisation plan as its Kerr step.
 #include "ssfm_kernels.h"
 using namespace plxs;
 
@@ -13,7 +14,13 @@ namespace {
 // interleaved transforms are read conflict-free.  Global loads are issued in
 // batches of COL_CH per thread before any arithmetic, to keep >= 64 KiB in flight
 // per CU.
-__global__ __launch_bounds__(COL_THREADS_MAX) void k_col_fwd(SsfmArgs a)
+// XPM (k_col_fwd_xpm): the Manakov cross-phase modulation of a dual-polarisation plan with several channels.
+// (The kernel is only reached with fls[3] = 1, so the weight x of the definition is 1 here.)
+// With H_k = s P_k I + (P - P_k) I + B, B = A - u_k u_k^H the coherency sum of the OTHER channels (A: k_stokes_sum's
+// record at the tile's own gather index), the step is u_k <- exp(-i g_k Leff H_k) u_k in closed form: H_k = h0 I + M with
+// M = [b1 c; conj(c) -b1] traceless, M^2 = b^2 I, so exp(-i t M) = cos(t b) I - i sin(t b)/b M.  Neither phase is bounded
+// by dphimax (sixteen channels: ~0.25 rad per step), hence the full-range sincos.
+template <bool XPM> __device__ __forceinline__ void col_fwd_body(const SsfmArgs &a)
 {
     PLX_DYN_LDS(lds);
     if (all_done_or_aborted(a)) return;
@@ -33,7 +40,45 @@ __global__ __launch_bounds__(COL_THREADS_MAX) void k_col_fwd(SsfmArgs a)
     const double leff = a.force ? a.f_leff : ctl->leff;
     const double gam = a.gam[c], gamleff = gam * leff;
     const int nel = N1 << a.logW;
-    if (a.dual) {
+    if (XPM) {
+        const cplx *rec = a.stokes + (((size_t)f << (a.p1 + a.p2)) << 1);
+        for (int e0 = tid; e0 < nel; e0 += nthr * COL_CH) {
+            cplx xv[COL_CH], yv[COL_CH], ra[COL_CH], rb[COL_CH];
+#pragma unroll
+            for (int k = 0; k < COL_CH; k++) {
+                const int e = min(e0 + k * nthr, nel - 1);
+                const size_t off = (size_t)(e >> a.logW) * N2 + col0 + (e & (W - 1));
+                xv[k] = a.ux[base + off]; yv[k] = a.uy[base + off];
+                ra[k] = rec[2 * off]; rb[k] = rec[2 * off + 1];
+            }
+#pragma unroll
+            for (int k = 0; k < COL_CH; k++) { pin(xv[k]); pin(yv[k]); pin(ra[k]); pin(rb[k]); }
+#pragma unroll
+            for (int k = 0; k < COL_CH; k++) {
+                const int e = e0 + k * nthr;
+                if (e >= nel) continue;
+                const cplx x = xv[k], y = yv[k];
+                const double pxx = x.x * x.x + x.y * x.y, pyy = y.x * y.x + y.y * y.y, Pk = pxx + pyy;
+                const double h0 = (a.spm ? Pk : 0.0) + 1.5 * ((ra[k].x + ra[k].y) - Pk);
+                const double b1 = 0.5 * ((ra[k].x - pxx) - (ra[k].y - pyy));
+                const double cr = rb[k].x - (x.x * y.x + x.y * y.y), ci = rb[k].y - (x.y * y.x - x.x * y.y);   // c = Bxy
+                const double b = sqrt(b1 * b1 + (cr * cr + ci * ci));
+                double s0, c0, st, ct;
+                sincos(-gamleff * h0, &s0, &c0);
+                sincos(gamleff * b, &st, &ct);
+                const double sb = b > 0 ? st / b : gamleff;        // sin(th)/b, finite where no neighbour has power
+                // M u = (b1 x + c y, conj(c) x - b1 y);  w = cos(th) u - i sb M u
+                const cplx mx = make_double2(b1 * x.x + (cr * y.x - ci * y.y), b1 * x.y + (cr * y.y + ci * y.x));
+                const cplx my = make_double2((cr * x.x + ci * x.y) - b1 * y.x, (cr * x.y - ci * x.x) - b1 * y.y);
+                const cplx wx = make_double2(ct * x.x + sb * mx.y, ct * x.y - sb * mx.x);
+                const cplx wy = make_double2(ct * y.x + sb * my.y, ct * y.y - sb * my.x);
+                const cplx nl = make_double2(c0, s0);
+                const int row = e >> a.logW, col = e & (W - 1);
+                s[(row << a.logT) + col] = cmul(wx, nl);
+                s[(row << a.logT) + W + col] = cmul(wy, nl);
+            }
+        }
+    } else if (a.dual) {
         for (int e0 = tid; e0 < nel; e0 += nthr * COL_CH) {
             cplx xv[COL_CH], yv[COL_CH];
 #pragma unroll
@@ -110,6 +155,10 @@ __global__ __launch_bounds__(COL_THREADS_MAX) void k_col_fwd(SsfmArgs a)
     }
 }
 
+__global__ __launch_bounds__(COL_THREADS_MAX) void k_col_fwd(SsfmArgs a) { col_fwd_body<false>(a); }
+
+__global__ __launch_bounds__(COL_THREADS_MAX) void k_col_fwd_xpm(SsfmArgs a) { col_fwd_body<true>(a); }
+
 // ------------------------------------------------------ pass 3: inverse columns ---
 // Completes ifft (1/N), applies the attenuation of the step (:531-532) and feeds
 // nextstep's global maximum (:694-696) -- no extra pass over the field.
@@ -179,5 +228,6 @@ __global__ __launch_bounds__(COL_THREADS_MAX) void k_col_inv(SsfmArgs a)
 
 namespace plxs {
 sweep_kernel_t col_fwd_kernel() { return k_col_fwd; }
+sweep_kernel_t col_fwd_xpm_kernel() { return k_col_fwd_xpm; }
 sweep_kernel_t col_inv_kernel() { return k_col_inv; }
 } // namespace plxs

@@ -27,6 +27,7 @@ typedef void (*colx_kernel_t)(SsfmArgs, int, int);
 
 // ---- selectors (defined next to the kernels) ----
 PLX_HIDDEN sweep_kernel_t col_fwd_kernel();                                       // ssfm_col.hip
+PLX_HIDDEN sweep_kernel_t col_fwd_xpm_kernel();                                   // (Manakov XPM between dual-polarisation channels)
 PLX_HIDDEN sweep_kernel_t col_inv_kernel();
 PLX_HIDDEN colx_kernel_t colx16_kernel(bool dual);                                // ssfm_colx.hip
 PLX_HIDDEN sweep_kernel_t row_kernel();                                           // ssfm_row.hip
@@ -40,6 +41,7 @@ PLX_HIDDEN void launch_umax(dim3 grid, hipStream_t st, const SsfmArgs &a);
 PLX_HIDDEN void launch_ctrl(int nframes, hipStream_t st, const SsfmArgs &a);
 PLX_HIDDEN void launch_compact(const FrameCtl *ctl, int nframes, int *active, int *nactive, int serves, hipStream_t st);
 PLX_HIDDEN void launch_rowsum(dim3 grid, hipStream_t st, const SsfmArgs &a);
+PLX_HIDDEN void launch_stokes_sum(dim3 grid, hipStream_t st, const SsfmArgs &a);
 PLX_HIDDEN void launch_pmd_tab(unsigned frames, hipStream_t st, const SsfmArgs &a);
 PLX_HIDDEN void launch_nl_att(unsigned grid, hipStream_t st, cplx *u, const double *gam, size_t N, int nfc, int spm, int xpm, double leff, double att);
 PLX_HIDDEN void launch_maxdiff(unsigned grid, hipStream_t st, const cplx *u, const cplx *uh, size_t n, unsigned long long *out);

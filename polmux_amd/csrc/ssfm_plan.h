@@ -28,6 +28,7 @@ struct plx_ssfm {
     size_t mbox_bytes = 0;
     int fused = 0, fused_grid = 0, tiles_pf = 0;
     uint32_t flags = 0;                      // plx_ssfm_create_ex
+    int xpm_dual = 0;                        // PLX_SSFM_XPM_MANAKOV on a multi-channel dual-polarisation plan: k_stokes_sum + k_col_fwd_xpm, d_psum holds the record
     int barrier_timeouts = 0;                // propagate calls of this plan that ended in a frame-barrier time-out (it then takes the three-sweep step
                                              // until plx_ssfm_barrier_timeouts(..., rearm) -- the gateway tier re-arms its cached plans itself)
     int calls_unfused = 0, rearm_after = 16; // gateway tier: three-sweep calls since the last time-out / how many of them before the fused step is tried again

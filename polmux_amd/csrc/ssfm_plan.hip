@@ -114,7 +114,7 @@ extern "C" int plx_ssfm_create_ex(plx_ssfm **out, const plx_ssfm_desc *desc, uin
 extern "C" int plx_ssfm_create_tuned(plx_ssfm **out, const plx_ssfm_desc *desc, uint32_t flags, const plx_ssfm_tuning *tuning)
 {
     if (!out || !desc) PLX_FAIL(PLX_ERR_ARG, "plx_ssfm_create: null argument");
-    if (flags & ~(uint32_t)PLX_SSFM_SHARE_DEVICE) PLX_FAIL(PLX_ERR_ARG, "plx_ssfm_create_ex: unknown flag");
+    if (flags & ~(uint32_t)(PLX_SSFM_SHARE_DEVICE | PLX_SSFM_XPM_MANAKOV)) PLX_FAIL(PLX_ERR_ARG, "plx_ssfm_create_ex: unknown flag");
     *out = nullptr;
     const int64_t N = desc->nfft;
     const int p = ilog2(N);
@@ -122,7 +122,9 @@ extern "C" int plx_ssfm_create_tuned(plx_ssfm **out, const plx_ssfm_desc *desc, 
         PLX_FAIL(PLX_ERR_UNSUPPORTED, "plx_ssfm_create: nfft must be a power of two in [256, 2^20]");
     if (desc->nfc < 1 || desc->max_frames < 1) PLX_FAIL(PLX_ERR_ARG, "plx_ssfm_create: nfc and max_frames must be >= 1");
     if (!desc->gam || !desc->betat) PLX_FAIL(PLX_ERR_ARG, "plx_ssfm_create: gam and betat are required");
-    if (desc->dual_pol && desc->fls[3] && desc->nfc > 1)
+    // Manakov XPM between separate dual-polarisation fields goes past the reference, on request only
+    const bool xpm_dual = desc->dual_pol && desc->fls[3] && desc->nfc > 1;
+    if (xpm_dual && !((flags & PLX_SSFM_XPM_MANAKOV) && desc->manakov))
         PLX_FAIL(PLX_ERR_REFERENCE, "The CNLSE with separate fields is not yet implemented"); // fiber.m:854
     if (desc->dual_pol && desc->fls[3] && desc->nfc == 1) { /* xpm flag is forced to 0 for one field, :224 */ }
     if (desc->nplates < 1) PLX_FAIL(PLX_ERR_ARG, "plx_ssfm_create: nplates must be >= 1");
@@ -132,6 +134,7 @@ extern "C" int plx_ssfm_create_tuned(plx_ssfm **out, const plx_ssfm_desc *desc, 
     else if (g_have_override) tune = g_override;
     else plx_ssfm_tuning_defaults(&tune);
     if (flags & PLX_SSFM_SHARE_DEVICE) tune.no_fuse = 1;      // the barrier-free three-sweep step: no co-residency requirement
+    if (xpm_dual) tune.no_fuse = 1;      // the fused sweep holds one channel's tile per workgroup and cannot see the others (as scalar XPM below)
 
     plx_ssfm *P = new plx_ssfm();
     P->d = *desc;
@@ -326,6 +329,10 @@ extern "C" int plx_ssfm_create_tuned(plx_ssfm **out, const plx_ssfm_desc *desc, 
               hipHostMalloc((void **)&P->h_ndone, 64, hipHostMallocDefault) == hipSuccess &&
               hipEventCreateWithFlags(&P->ev, hipEventDisableTiming) == hipSuccess;
     if (ok && !a.dual && a.xpm) ok = hipMalloc((void **)&P->d_psum, sizeof(double) * (size_t)F * N) == hipSuccess;
+    // Manakov XPM between dual-polarisation channels: the same pointer holds the coherency record of k_stokes_sum,
+    // [F][N] x {Axx, Ayy, Re Axy, Im Axy}
+    P->xpm_dual = xpm_dual ? 1 : 0;
+    if (ok && xpm_dual) ok = hipMalloc((void **)&P->d_psum, sizeof(double) * 4 * (size_t)F * N) == hipSuccess;
     if (!ok) { free_plan(P); PLX_FAIL(PLX_ERR_HIP, "plx_ssfm_create: device allocation failed"); }
     a.betat_p = P->d_betat; a.db1_p = P->d_db1; a.tpass = P->d_tpass; a.tw1 = P->d_tw1; a.tw2 = P->d_tw2; a.ctab = P->d_ctab; a.tw2c = P->d_tw2c; a.twmid = P->d_twmid;
     a.gam = P->d_gam; a.ctl = P->d_ctl; a.umax = P->d_umax; a.ndone = P->d_ndone; a.psum = P->d_psum;
@@ -338,7 +345,7 @@ extern "C" int plx_ssfm_create_tuned(plx_ssfm **out, const plx_ssfm_desc *desc, 
                                                             // 256 by 3-12 %; tall tiles of large frames: one workgroup per CU, 16 waves
     if (tune.col_threads == 128 || tune.col_threads == 256 || tune.col_threads == 512 || tune.col_threads == 1024) P->col_threads = tune.col_threads;
     if (allow_lds(colx16_kernel(true), P->lds_col) != hipSuccess || allow_lds(colx16_kernel(false), P->lds_col) != hipSuccess || allow_lds(col_fwd_kernel(), P->lds_col) != hipSuccess ||
-        allow_lds(col_inv_kernel(), P->lds_col) != hipSuccess ||
+        allow_lds(col_inv_kernel(), P->lds_col) != hipSuccess || (P->xpm_dual && allow_lds(col_fwd_xpm_kernel(), P->lds_col) != hipSuccess) ||
         (!P->tw_compact && allow_lds(row_kernel(), P->lds_row > P->rs_lds ? P->lds_row : P->rs_lds) != hipSuccess) ||
         (P->tw_compact && (allow_lds(row4k_kernel(false, false), P->rs_lds) != hipSuccess || allow_lds(row4k_kernel(true, false), P->rs_lds_pair) != hipSuccess ||
                            allow_lds(row4k_kernel(false, true), P->rs_lds) != hipSuccess))) {
@@ -659,9 +666,14 @@ static int propagate_frames(plx_ssfm *P, cplx *d_ux, cplx *d_uy, int nframes, hi
                 if (gx > 256) gx = 256;
                 launch_rowsum(dim3(gx, (unsigned)nframes), st, a);
             }
+            if (P->xpm_dual) {               // Manakov XPM: the coherency sums of the channels, once per frame and step
+                unsigned gx = (unsigned)((P->N + 255) / 256);
+                if (gx > 256) gx = 256;
+                launch_stokes_sum(dim3(gx, (unsigned)nframes), st, a);
+            }
             if (a.e1tab) launch_pmd_tab(FC / nfc, st, a);
             PLX_MARK(0, steps + sidx);
-            launch(col_fwd_kernel(), gcol, bcol, P->lds_col, st, a);
+            launch(P->xpm_dual ? col_fwd_xpm_kernel() : col_fwd_kernel(), gcol, bcol, P->lds_col, st, a);
             PLX_MARK(1, steps + sidx);
             launch_row(P, a, FC, st);
             PLX_MARK(2, steps + sidx);

@@ -1,6 +1,7 @@
 // ssfm_small.hip -- the small kernels of the split-step Fourier propagator: nextstep's initial maximum, the one-lane-per-frame
-// step controller, the active list, the trunk phasor tables of PMD plans, scalar XPM's row sums and the element-wise pieces
-// of the adaptive-step scheme (fiber.m:682-758, :795, :925, :938-1009).
+// step controller, the active list, the trunk phasor tables of PMD plans, scalar XPM's row sums, the coherency sums of Manakov
+// XPM between dual-polarisation channels and the element-wise pieces of the adaptive-step scheme (fiber.m:682-758, :795, :925,
+// :938-1009).
 #include "ssfm_ctrl.h"
 #include "ssfm_kernels.h"
 using namespace plxs;
@@ -125,6 +126,48 @@ __global__ __launch_bounds__(256) void k_rowsum(SsfmArgs a)
     }
 }
 
+// ---------------------- Manakov XPM between dual-polarisation channels ---
+// The coherency sum A = sum_j u_j u_j^H of a frame's channels per time sample, {Axx, Ayy, Re Axy, Im Axy} with
+// Axy = sum x_j conj(y_j): what k_col_fwd_xpm needs of the OTHER channels (it subtracts its own).  One lane per sample
+// (16-B loads, consecutive lanes on consecutive samples), STOKES_CH channels' loads issued before any arithmetic.
+#define STOKES_CH 4
+__global__ __launch_bounds__(256) void k_stokes_sum(SsfmArgs a)
+{
+    const int f = blockIdx.y;
+    if (a.ctl[f].done) return;
+    const size_t N = (size_t)1 << (a.p1 + a.p2);
+    const cplx *ux = a.ux + (size_t)f * a.nfc * N, *uy = a.uy + (size_t)f * a.nfc * N;
+    cplx *rec = a.stokes + 2 * (size_t)f * N;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < N; i += (size_t)gridDim.x * blockDim.x) {
+        double axx = 0, ayy = 0, axr = 0, axi = 0;
+        int k = 0;
+        for (; k + STOKES_CH <= a.nfc; k += STOKES_CH) {
+            cplx xv[STOKES_CH], yv[STOKES_CH];
+#pragma unroll
+            for (int j = 0; j < STOKES_CH; j++) { xv[j] = ux[(size_t)(k + j) * N + i]; yv[j] = uy[(size_t)(k + j) * N + i]; }
+#pragma unroll
+            for (int j = 0; j < STOKES_CH; j++) { pin(xv[j]); pin(yv[j]); }
+#pragma unroll
+            for (int j = 0; j < STOKES_CH; j++) {
+                const cplx x = xv[j], y = yv[j];
+                axx += x.x * x.x + x.y * x.y;
+                ayy += y.x * y.x + y.y * y.y;
+                axr += x.x * y.x + x.y * y.y;
+                axi += x.y * y.x - x.x * y.y;
+            }
+        }
+        for (; k < a.nfc; k++) {
+            const cplx x = ux[(size_t)k * N + i], y = uy[(size_t)k * N + i];
+            axx += x.x * x.x + x.y * x.y;
+            ayy += y.x * y.x + y.y * y.y;
+            axr += x.x * y.x + x.y * y.y;
+            axi += x.y * y.x - x.x * y.y;
+        }
+        rec[2 * i] = make_double2(axx, ayy);
+        rec[2 * i + 1] = make_double2(axr, axi);
+    }
+}
+
 // Row and column phasors of every trunk of the step each listed frame is about to make (see SsfmArgs::e1tab).  One workgroup
 // per frame; runs between the step controller (k_ctrl / the fused sweep, which leave ntrunk, dzb_first, dzb_last in the
 // frame's record) and the row pass.
@@ -168,6 +211,7 @@ void launch_compact(const FrameCtl *ctl, int nframes, int *active, int *nactive,
     PLX_LAUNCH(k_compact, dim3(1), dim3(COMPACT_THREADS), COMPACT_THREADS * sizeof(int), st, ctl, nframes, active, nactive, serves);
 }
 void launch_rowsum(dim3 grid, hipStream_t st, const SsfmArgs &a) { PLX_LAUNCH(k_rowsum, grid, dim3(256), 0, st, a); }
+void launch_stokes_sum(dim3 grid, hipStream_t st, const SsfmArgs &a) { PLX_LAUNCH(k_stokes_sum, grid, dim3(256), 0, st, a); }
 void launch_pmd_tab(unsigned frames, hipStream_t st, const SsfmArgs &a) { PLX_LAUNCH(k_pmd_tab, dim3(frames), dim3(256), 0, st, a); }
 void launch_nl_att(unsigned grid, hipStream_t st, cplx *u, const double *gam, size_t N, int nfc, int spm, int xpm, double leff, double att)
 {

@@ -126,6 +126,12 @@ def fiber(x, flag=None, rng=None):
         raise ValueError("create_field must be called before fiber")
     fx = GSTATE.FIELDX
     nfc, nfft = fx.shape
+    # x.xpm_dualpol = 'manakov' (with x.manakov = 'yes'): cross-phase modulation between dual-polarisation 'sepfields'
+    # channels, which the reference leaves unimplemented (fiber.m:854) -- DESIGN.md section 8c, PLX_SSFM_XPM_MANAKOV
+    xpm_dualpol = x.get("xpm_dualpol")
+    if xpm_dualpol not in (None, "manakov"):
+        raise ValueError("xpm_dualpol must be 'manakov' when given")
+    pflags = _abi.PLX_SSFM_XPM_MANAKOV if xpm_dualpol else 0
     if not _has(x, "dzmax") or x["dzmax"] > x["length"]:
         x["dzmax"] = x["length"]                                              # :139-141
     tolflag = 0
@@ -193,8 +199,8 @@ def fiber(x, flag=None, rng=None):
         GSTATE.FIELDX = to_device_field(ur + 1j * ui)
         fiber.last = dict(firstdz=first.value, ncycle=ncyc.value, nrej=nrej.value)
         return None
-    key = (nfft, nfc, int(isv), tuple(fls), dzmaxt, dphimaxt, t["alphalin"], x["length"], nplates, manakov,
-           gam.tobytes(), t["betat"].tobytes(), t["db1"].tobytes())
+    key =(nfft, nfc, int(isv), tuple(fls), dzmaxt, dphimaxt, t["alphalin"], x["length"], nplates, manakov,
+           gam.tobytes(), t["betat"].tobytes(), t["db1"].tobytes(), pflags)
 
     def build():
         d = _abi.SsfmDesc()
@@ -205,7 +211,7 @@ def fiber(x, flag=None, rng=None):
         d.nplates, d.manakov = nplates, int(manakov)
         d.gam, d.betat, d.db1 = gam.ctypes.data, t["betat"].ctypes.data, t["db1"].ctypes.data
         p = C.c_void_p()
-        lib.call("plx_ssfm_create", C.byref(p), C.byref(d))
+        lib.call("plx_ssfm_create_ex", C.byref(p), C.byref(d), pflags)
         return (p, d)
 
     plan = _plan_for(hash(key), build)[0]

@@ -49,7 +49,8 @@ class HotPathConfig:
                  polmethod="cma", cma_taps=7, cma_mu=1 / 6000, freqavg=500, phasavg=3, poworder=2,
                  frontend="pick", oftype="gauss", obw=1.9, oord=3, eftype="bessel5", ebw=0.65, eord=4, lopower=0.0,
                  adcbits=5, span_nf_db=None, rx_amp=False, variants=1, nch=1, chspacing=0.4, share_device=False,
-                 equaliser="cde", dbp_steps=4, dbp_xi=1.0, tx_linewidth=0.0, lo_linewidth=0.0, decoding="rotation"):
+                 equaliser="cde", dbp_steps=4, dbp_xi=1.0, tx_linewidth=0.0, lo_linewidth=0.0, decoding="rotation",
+                 xpm_dualpol=None):
         """frontend: 'pick' = 2-sps sampling supplied by the harness; 'cohmix' = the reference's own
         receiver_cohmix + ADC + decimate chain (RxPdmCohQpsk.m, Run_my_PDM_QPSK.m:52-73 defaults) on the device.
         nspans > 1: every span but the last is followed by an in-line flat amplifier restoring its loss
@@ -77,7 +78,11 @@ class HotPathConfig:
         on the picked 2-sps samples (pick).  0: no phase noise, nothing is launched.
         decoding: 'rotation' = errors_resolved's minimum over the pi/2 rotations and the polarisation swap; 'dqpsk' = the
         Monte-Carlo scripts' differential decoding of both patterns plus ex20's swap rule (errors_dqpsk); McCampaign counts
-        with it."""
+        with it.
+        xpm_dualpol: None = the reference's behaviour (an 'x' flag on dual-polarisation 'sepfields' frames raises its
+        "not yet implemented"); 'manakov' = cross-phase modulation between the nch channels in the Manakov form (DESIGN.md
+        section 8c, PLX_SSFM_XPM_MANAKOV) with flag 'gpsx' / '-psx' / 'gp-x' / '-p-x' and manakov='yes'; not with
+        equaliser='dbp', which has no XPM backpropagation."""
         self.__dict__.update(locals())
         del self.__dict__["self"]
 
@@ -99,6 +104,10 @@ class HotPath:
                 raise ValueError("%s must be a finite scalar >= 0 (normalised to the symbol rate)" % name)
         if cfg.decoding not in ("rotation", "dqpsk"):
             raise ValueError("decoding must be 'rotation' or 'dqpsk'")
+        if cfg.xpm_dualpol not in (None, "manakov"):
+            raise ValueError("xpm_dualpol must be None or 'manakov'")
+        if cfg.xpm_dualpol and cfg.equaliser == "dbp":
+            raise ValueError("equaliser='dbp' has no XPM backpropagation: not with xpm_dualpol")
         self.torch = torch
         self.cfg = cfg
         self.F = int(max_frames)
@@ -129,7 +138,8 @@ class HotPath:
         self._keep = (np.ascontiguousarray(t["gam"]), t["betat"], t["db1"])
         d.gam, d.betat, d.db1 = (a.ctypes.data for a in self._keep)
         self.ssfm = C.c_void_p()
-        self.lib.call("plx_ssfm_create_ex", C.byref(self.ssfm), C.byref(d), _abi.PLX_SSFM_SHARE_DEVICE if cfg.share_device else 0)
+        self.lib.call("plx_ssfm_create_ex", C.byref(self.ssfm), C.byref(d), (_abi.PLX_SSFM_SHARE_DEVICE if cfg.share_device else 0)
+                      | (_abi.PLX_SSFM_XPM_MANAKOV if cfg.xpm_dualpol else 0))
         self.nplates = nplates
         self._profiling = False
         if self.pmd:   # Monte-Carlo style: an independent random birefringence draw per frame (fiber.m:274-276)
