@@ -421,6 +421,22 @@ int plx_phase_noise_dev(double *d_ux, double *d_uy, int64_t stride, int64_t pitc
                         int32_t nfc, int nframes, const double *sigma, uint64_t seed, const int64_t *d_keys,
                         int32_t tag, const double *d_phi_in, double *d_phi_out, double *d_work, void *stream);
 
+/* ------------------------------------------------------- a WDM comb as one field --- */
+/* create_field('unique') (create_field.m:165-199) in the time domain, and the channel selection of
+ * receiver_cohmix.m:104-125 with a per-channel delay taken out.  N = nfft, s_c = shift[c] the carrier offset of channel c in
+ * frequency bins (ndfn of create_field.m:181-184), W(k) = exp(-i 2 pi (k mod N) / N):
+ *   mux      u[f][n]    = sum_{c < nch} s[f][c][n] * W(s_c n)                       (c ascending; X and Y share the phasor)
+ *   select   r[f][c][n] = u[f][m] * conj(W(s_c m)),  m = (n + delay[c]) mod N       (the phasor at the SOURCE index m)
+ * s_c n is reduced modulo N in integers, so no error grows with n; a channel at shift 0 is copied to the bit.
+ * d_sx, d_sy / d_rx, d_ry: [nframes][nch][nfft] complex128 (the 'sepfields' layout); d_ux, d_uy: [nframes][nfft].  The Y
+ * pointers may be NULL together (one polarisation).  nfft: power of two in [256, 2^20]; 1 <= nch <= 64; |shift[c]| < nfft/2;
+ * |delay[c]| < nfft (delay NULL: no delay).  shift and delay are HOST arrays [nch], copied into the kernel's argument block:
+ * no allocation, no synchronisation, nothing but the launch on `stream`.                                                  */
+int plx_wdm_mux_dev(const double *d_sx, const double *d_sy, double *d_ux, double *d_uy, int64_t nfft, int32_t nch,
+                    int nframes, const int64_t *shift, void *stream);
+int plx_wdm_select_dev(const double *d_ux, const double *d_uy, double *d_rx, double *d_ry, int64_t nfft, int32_t nch,
+                       int nframes, const int64_t *shift, const int64_t *delay, void *stream);
+
 /* ------------------------------------------------------------ coherent front end --- */
 /* The step between fiber() and CDE_OFDE(): receiver_cohmix.m:165-307 (optical filter x post-compensation,
  * LO mixing in two 90-degree hybrids, balanced or single photodiodes, electrical low-pass) followed by

@@ -133,6 +133,8 @@ SIGNATURES = {
     "plx_ampliflat_dev": [_vp, _vp, _i64, _i32, C.c_int, _dbl, _vp, _vp, C.c_uint64, _vp, _i32, _i32, _vp],
     "plx_phase_noise_dev": [_vp, _vp, _i64, _i64, _dbl, _i64, _i32, C.c_int, _vp, C.c_uint64, _vp, _i32, _vp, _vp, _vp,
                             _vp],
+    "plx_wdm_mux_dev": [_vp, _vp, _vp, _vp, _i64, _i32, C.c_int, _vp, _vp],
+    "plx_wdm_select_dev": [_vp, _vp, _vp, _vp, _i64, _i32, C.c_int, _vp, _vp, _vp],
     "plx_front_create": [C.POINTER(_vp), C.POINTER(FrontDesc)],
     "plx_front_destroy": [_vp],
     "plx_front_out_len": [_vp],

@@ -59,7 +59,8 @@ def parse_flag(flag, nfc, x):
 
 
 def fiber_tables(x, fls, nfc, dgdrms_symbols):
-    """Physical conversions, fiber.m:302-362.  Returns dict(alphalin, gam, betat, db1, b1, Dch)."""
+    """Physical conversions, fiber.m:302-362.  Returns dict(alphalin, gam, betat, db1, b1, Dch, beta2, b30): beta2 [nfc] and
+    b30 are the coefficients behind betat (:330-332, :309-311)."""
     CL = CONSTANTS.CLIGHT
     lam, disp, slope = _get(x, "lambda"), _get(x, "disp"), _get(x, "slope")
     alphalin = (math.log(10) * 1e-4) * _get(x, "alphadB")                    # :302
@@ -91,7 +92,7 @@ def fiber_tables(x, fls, nfc, dgdrms_symbols):
         betat[:, k] = omega * beta1[k] + 0.5 * omega ** 2 * beta2[k] + omega ** 3 * b30 / 6   # :355-356
         if fls[1] == 1:
             db1[:, k] = dgdrms_symbols / GSTATE.SYMBOLRATE * omega            # :284,358
-    return dict(alphalin=alphalin, gam=gam, betat=betat, db1=db1, b1=b1, Dch=Dch)
+    return dict(alphalin=alphalin, gam=gam, betat=betat, db1=db1, b1=b1, Dch=Dch, beta2=beta2, b30=b30)
 
 
 _plans = {}

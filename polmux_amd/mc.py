@@ -283,6 +283,11 @@ class ShardedBer:
             # error counts and, when a continuous sample travels with them, the BIT PATTERNS of the float64 samples in the
             # second half of the same int64 buffer.  Slots are disjoint (every other rank holds 0 there), so SUM is exact
             # for both halves.
+            if len(local) != len(mine):
+                # (a 'unique' WDM campaign, DESIGN.md 8d: McCampaign returns a count per channel-frame, [n nch])
+                raise ValueError("ShardedBer needs one error count per realisation: the simulator returned %d for %d "
+                                 "(per-channel-frame counts of a wdm_field='unique' campaign with nch > 1 are not accepted)"
+                                 % (len(local), len(mine)))
             with_s = self.x_samples is not None and launch is not None
             vec = torch.zeros(n_round * (2 if with_s else 1), dtype=torch.int64, device=self.device or "cpu")
             if mine:

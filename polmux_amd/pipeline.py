@@ -50,7 +50,7 @@ class HotPathConfig:
                  frontend="pick", oftype="gauss", obw=1.9, oord=3, eftype="bessel5", ebw=0.65, eord=4, lopower=0.0,
                  adcbits=5, span_nf_db=None, rx_amp=False, variants=1, nch=1, chspacing=0.4, share_device=False,
                  equaliser="cde", dbp_steps=4, dbp_xi=1.0, tx_linewidth=0.0, lo_linewidth=0.0, decoding="rotation",
-                 xpm_dualpol=None):
+                 xpm_dualpol=None, wdm_field="sepfields", mux_filter=None):
         """frontend: 'pick' = 2-sps sampling supplied by the harness; 'cohmix' = the reference's own
         receiver_cohmix + ADC + decimate chain (RxPdmCohQpsk.m, Run_my_PDM_QPSK.m:52-73 defaults) on the device.
         nspans > 1: every span but the last is followed by an in-line flat amplifier restoring its loss
@@ -82,7 +82,17 @@ class HotPathConfig:
         xpm_dualpol: None = the reference's behaviour (an 'x' flag on dual-polarisation 'sepfields' frames raises its
         "not yet implemented"); 'manakov' = cross-phase modulation between the nch channels in the Manakov form (DESIGN.md
         section 8c, PLX_SSFM_XPM_MANAKOV) with flag 'gpsx' / '-psx' / 'gp-x' / '-p-x' and manakov='yes'; not with
-        equaliser='dbp', which has no XPM backpropagation."""
+        equaliser='dbp', which has no XPM backpropagation.
+        wdm_field: 'sepfields' = one column per channel (above); 'unique' = the frame is ONE dual-polarisation field carrying
+        every channel at its carrier offset (create_field.m:165-199), which sees the whole Kerr nonlinearity of the comb
+        (SPM, XPM and four-wave mixing) -- DESIGN.md section 8d: multiplexed on the device (plx_wdm_mux_dev), propagated by a
+        one-column plan at the centre wavelength, and split back into channel-frames with the walk-off delay taken out
+        (plx_wdm_select_dev) in front of the receivers; with the 'pick' front end every channel-frame then passes the
+        optical filter (oftype, obw, oord), which isolates it from its neighbours.  Not with equaliser='dbp', not with
+        xpm_dualpol.
+        mux_filter: None, or dict(ftype=, bw=, ord=) -- the multiplexer's channel filter, 'unique' only: every Tx waveform
+        is band-limited once on the host, ifft(fft(v) myfilter(ftype, FN, 0.5 bw, ord)) (bw two-sided, in symbol rates,
+        like obw), and rescaled to pavg_mw.  None is the reference's create_field: nothing is filtered."""
         self.__dict__.update(locals())
         del self.__dict__["self"]
 
@@ -91,9 +101,48 @@ class HotPathConfig:
         return self.nsymb * self.nt
 
 
+def check_wdm_options(cfg):
+    """The raises of HotPathConfig's wdm_field / mux_filter (needs no GPU); returns True for a 'unique' field."""
+    field, mf = cfg.wdm_field, cfg.mux_filter
+    if not isinstance(field, str) or field not in ("sepfields", "unique"):
+        raise ValueError("wdm_field must be 'sepfields' or 'unique'")
+    if mf is not None:
+        if not isinstance(mf, dict) or "ftype" not in mf or "bw" not in mf or set(mf) - {"ftype", "bw", "ord"}:
+            raise ValueError("mux_filter must be None or dict(ftype=..., bw=...[, ord=...])")
+        if not (np.ndim(mf["bw"]) == 0 and math.isfinite(float(mf["bw"])) and float(mf["bw"]) > 0):
+            raise ValueError("mux_filter: bw must be a finite scalar > 0 (two-sided, in symbol rates)")
+        if field == "sepfields":
+            raise ValueError("mux_filter needs wdm_field='unique' (it would change the 'sepfields' frames)")
+    if field == "unique":
+        if cfg.equaliser == "dbp":
+            raise ValueError("wdm_field='unique' has no digital backpropagation: not with equaliser='dbp'")
+        if cfg.xpm_dualpol:
+            raise ValueError("wdm_field='unique' carries the channels' cross-phase modulation in its one field: not with xpm_dualpol")
+    return field == "unique"
+
+
+def wdm_walkoff(shifts, beta2, b30, total_length, symbolrate, dfn, nt):
+    """Walk-off of the channels of a 'unique' field after total_length metres: (delay_symbols, delay).  Channel c sits at
+    Om_c = -2 pi symbolrate dfn s_c (where plx_wdm_mux_dev put it: on an integer bin, not at its unrounded wavelength);
+    delay_symbols = total_length symbolrate (beta2 Om_c + b30 Om_c^2 / 2) with the one-column beta2, b30 of fiber_tables;
+    delay = MATLAB's round(delay_symbols nt) in samples: plx_wdm_select_dev reads the field at n + delay[c]."""
+    om = -2 * math.pi * symbolrate * dfn * np.asarray(shifts, dtype=float)
+    ds = total_length * symbolrate * (beta2 * om + 0.5 * b30 * om * om)
+    v = ds * nt
+    return ds, (np.sign(v) * np.floor(np.abs(v) + 0.5)).astype(np.int64)
+
+
+def band_limit(vx, vy, h, pavg_mw):
+    """the multiplexer's channel filter on one Tx waveform: ifft(fft(v) h), rescaled to the average power pavg_mw"""
+    fx, fy = np.fft.ifft(np.fft.fft(vx) * h), np.fft.ifft(np.fft.fft(vy) * h)
+    k = math.sqrt(pavg_mw / np.mean(np.abs(fx) ** 2 + np.abs(fy) ** 2))
+    return fx * k, fy * k
+
+
 class HotPath:
     def __init__(self, cfg, max_frames):
         import torch
+        self.unique = check_wdm_options(cfg)
         if cfg.equaliser not in ("cde", "dbp"):
             raise ValueError("equaliser must be 'cde' or 'dbp'")
         if cfg.equaliser == "dbp" and cfg.frontend != "pick":
@@ -123,14 +172,15 @@ class HotPath:
         GSTATE.LAMBDA = cfg.lam + cfg.chspacing * (np.arange(nch) - (nch - 1) / 2)      # lasersource.m: equally spaced comb
         x = {"length": cfg.length, "alphadB": cfg.alphadB, "aeff": cfg.aeff, "n2": cfg.n2, "lambda": cfg.lam,
              "disp": cfg.disp, "slope": cfg.slope, "dphimax": cfg.dphimax, "dzmax": min(cfg.dzmax, cfg.length)}
-        self.fls, dphimaxt, dzmaxt = parse_flag(cfg.flag, nch, x)
+        nfc = self.nfc = 1 if self.unique else nch       # columns of the fibre plan: a 'unique' field is one
+        self.fls, dphimaxt, dzmaxt = parse_flag(cfg.flag, nfc, x)
         self.pmd = self.fls[1] == 1
         nplates = cfg.nplates if self.pmd else 1
         dgdrms = math.sqrt(3 * math.pi / 8) * cfg.dgd / math.sqrt(nplates) if self.pmd else 0.0   # fiber.m:277
-        t = fiber_tables(x, self.fls, nch, dgdrms)
+        t = fiber_tables(x, self.fls, nfc, dgdrms)        # (one column: the centre wavelength lamc and its gamma, as fiber())
         self.alphalin = t["alphalin"]
         d = _abi.SsfmDesc()
-        d.nfft, d.nfc, d.dual_pol, d.max_frames = n, nch, 1, self.F
+        d.nfft, d.nfc, d.dual_pol, d.max_frames = n, nfc, 1, self.F
         for i in range(4):
             d.fls[i] = self.fls[i]
         d.dzmaxt, d.dphimaxt, d.alphalin, d.length = dzmaxt, dphimaxt, t["alphalin"], cfg.length
@@ -146,6 +196,12 @@ class HotPath:
             self.set_random_pmd(range(self.F))
         # --- Tx (host, once): Run_my_PDM_QPSK.m:101-117 ---
         ux, uy, bits, power = synth.pdm_qpsk_field(cfg.nsymb, cfg.nt, cfg.pavg_mw)
+        hmux = None
+        mf = cfg.mux_filter
+        if mf is not None:                               # the multiplexer's channel filter (host, once per plan)
+            from .rxfront import myfilter
+            hmux = myfilter(mf["ftype"], GSTATE.FN, 0.5 * float(mf["bw"]), mf.get("ord"))
+            ux, uy = band_limit(ux, uy, hmux, cfg.pavg_mw)
         self.tx_host = (ux, uy)
         self.bits = bits
         self.power_mw = power
@@ -158,6 +214,8 @@ class HotPath:
         for v in range(1, max(1, int(cfg.variants))):
             vx, vy, vb, vp = synth.pdm_qpsk_field(cfg.nsymb, cfg.nt, cfg.pavg_mw, (2 + 2 * v) % maxseed, (3 + 2 * v) % maxseed)
             assert abs(vp - power) <= 1e-9 * power      # de Bruijn sequences share their symbol statistics
+            if hmux is not None:
+                vx, vy = band_limit(vx, vy, hmux, cfg.pavg_mw)
             self.var_host.append((vx, vy, vb))
         self.nvar = len(self.var_host)
         if self.nvar > 1:
@@ -169,6 +227,17 @@ class HotPath:
         self.dpat = torch.from_numpy(dv[0]).to(self.dev)
         if self.nvar > 1:
             self.dpat_frames = torch.from_numpy(dv[np.arange(self.CF) % self.nvar].copy()).to(self.dev)
+        if self.unique:
+            # the comb as one field: carrier offsets in bins (create_field.m:181-184; raises when NT is too small for the
+            # comb), the walk-off select takes out, and the plan-owned field the fibre works on
+            from .gstate import unique_field_shifts
+            self.wdm_shift = np.ascontiguousarray(unique_field_shifts(), dtype=np.int64)
+            self.wdm_delay_symbols, self.wdm_delay = wdm_walkoff(self.wdm_shift, float(t["beta2"][0]), float(t["b30"]),
+                                                                 cfg.nspans * cfg.length, cfg.symbolrate,
+                                                                 GSTATE.FN[1] - GSTATE.FN[0], cfg.nt)
+            self.wdm_delay = np.ascontiguousarray(self.wdm_delay)
+            self.wx = torch.empty((self.F, n), dtype=torch.complex128, device=self.dev)
+            self.wy = torch.empty_like(self.wx)
         self._phase_work = {}                            # tile sums of the phase generator, per laser (allocated on use)
         self._lo_buf = None                              # [F nch, nfft] LO phase of the cohmix route (allocated on use)
         self.rx_gain = None                              # per-frame receiver scale of a launch-power ladder (make_batch)
@@ -219,6 +288,16 @@ class HotPath:
             self.front = rxfront._Front(n, True, self.CF, hopt, elo, hel, True, cfg.adcbits, r, self.front_tables["fir"])
         elif cfg.frontend != "pick":
             raise ValueError("frontend must be 'pick' or 'cohmix'")
+        self.chfilt = None
+        if self.unique and nch > 1 and self.front is None:
+            # the pick has no optical filter of its own: a channel-frame cut out of the one field still has its neighbours
+            # beside it in the spectrum (one channel has none: nch = 1 is the one-channel path)
+            from .rxfront import myfilter
+            hch = np.asarray(myfilter(cfg.oftype, GSTATE.FN, 0.5 * cfg.obw, cfg.oord), dtype=complex)
+            self.chfilt_h = hch
+            hr, hi = np.ascontiguousarray(hch.real), np.ascontiguousarray(hch.imag)
+            self.chfilt = C.c_void_p()
+            self.lib.call("plx_filter_create", C.byref(self.chfilt), n, self.CF, hr.ctypes.data, hi.ctypes.data)
         c128 = torch.complex128
         self.rx = torch.empty((self.CF, 2, self.Lrx), dtype=c128, device=self.dev)
         self.eq = torch.empty_like(self.rx)
@@ -226,10 +305,11 @@ class HotPath:
         self.err = torch.zeros((self.CF, 2), dtype=torch.int64, device=self.dev)
 
     def close(self):
-        for name, h in (("plx_ssfm_destroy", self.ssfm), ("plx_cde_destroy", self.cde), ("plx_dsp_destroy", self.dsp)):
+        for name, h in (("plx_ssfm_destroy", self.ssfm), ("plx_cde_destroy", self.cde), ("plx_dsp_destroy", self.dsp),
+                        ("plx_filter_destroy", self.chfilt)):
             if h:
                 self.lib.call(name, h)
-        self.ssfm = self.cde = self.dsp = None
+        self.ssfm = self.cde = self.dsp = self.chfilt = None
         if self.dbp is not None:
             self.dbp.close()
             self.dbp = None
@@ -292,16 +372,25 @@ class HotPath:
         one entry per amplifier, of [F, 2, n] complex128 device tensors used INSTEAD of the device generator
         (ampliflat's options.noise, ampliflat.m:123-129: the parity route).
         tx_phase: optional [F, nch, n] float64 device tensor, the transmitter lasers' phase used INSTEAD of the
-        cfg.tx_linewidth generator (keyed by span_keys, or the frame index): both polarisations *= exp(+i phi)."""
+        cfg.tx_linewidth generator (keyed by span_keys, or the frame index): both polarisations *= exp(+i phi).
+        wdm_field='unique': the same contract -- the channels of ux, uy (after their lasers' phase) are multiplexed into the
+        plan's one field self.wx, self.wy [F, n], the spans and amplifiers work on that, and on return channel c of frame f
+        in ux, uy holds that channel cut back out at baseband with its walk-off taken out (not yet filtered: its
+        neighbours are still beside it in the spectrum); self.wx[:F], self.wy[:F] keep the one field."""
         F = ux.shape[0]
         self._rows = self._steps = 0
         cfg = self.cfg
         if tx_phase is not None or cfg.tx_linewidth > 0:      # lasersource.m:182-192: one laser feeds X and Y
             self._phase(ux.data_ptr(), uy.data_ptr(), 1, cfg.nfft, 1.0, F, span_keys, _abi.PLX_PHASE_TX, cfg.tx_linewidth,
                         tx_phase)
+        px, py = ux.data_ptr(), uy.data_ptr()
+        if self.unique:
+            px, py = self.wx.data_ptr(), self.wy.data_ptr()
+            self.lib.call("plx_wdm_mux_dev", ux.data_ptr(), uy.data_ptr(), px, py, cfg.nfft, self.nch, F,
+                          self.wdm_shift.ctypes.data, self.stream())
         namp = 0
         for span in range(cfg.nspans):
-            self.lib.call("plx_ssfm_propagate_dev", self.ssfm, ux.data_ptr(), uy.data_ptr(), F, self.stream())
+            self.lib.call("plx_ssfm_propagate_dev", self.ssfm, px, py, F, self.stream())
             rows, steps = C.c_int64(), C.c_int64()
             self.lib.call("plx_ssfm_stats", self.ssfm, C.byref(rows), C.byref(steps))
             self._rows += rows.value
@@ -311,16 +400,19 @@ class HotPath:
                 sig = None
                 if cfg.span_nf_db is not None:
                     from .ampliflat import ase_sigma
-                    sig = np.ascontiguousarray(ase_sigma(cfg.span_nf_db, gain, self.nch), dtype=float)
+                    sig = np.ascontiguousarray(ase_sigma(cfg.span_nf_db, gain, self.nfc), dtype=float)
                 kt = None
                 if span_keys is not None:
                     kt = self.torch.as_tensor(np.asarray(list(span_keys), dtype=np.int64), device=self.dev)
                 inj = inject_noise[namp] if inject_noise is not None else None
-                self.lib.call("plx_ampliflat_dev", ux.data_ptr(), uy.data_ptr(), cfg.nfft, self.nch, F, gain,
+                self.lib.call("plx_ampliflat_dev", px, py, cfg.nfft, self.nfc, F, gain,
                               sig.ctypes.data if sig is not None else None, inj.data_ptr() if inj is not None else None,
                               (20260101 + 7919 * span) & (2 ** 64 - 1),
                               kt.data_ptr() if kt is not None else None, 1, 1, self.stream())
                 namp += 1
+        if self.unique:
+            self.lib.call("plx_wdm_select_dev", px, py, ux.data_ptr(), uy.data_ptr(), cfg.nfft, self.nch, F,
+                          self.wdm_shift.ctypes.data, self.wdm_delay.ctypes.data, self.stream())
 
     def _phase(self, pu, pv, stride, pitch, sign, F, keys, tag, linewidth, phi_in, phi_out=None):
         """one plx_phase_noise_dev call on F frames of nch channels: the injected phi_in, or the generator keyed by keys"""
@@ -404,6 +496,9 @@ class HotPath:
                             lop.data_ptr())
             self.front.run(ux, uy, self.front_shifts, out=rx, lo_phase=lop)
         else:
+            if self.chfilt is not None:        # 'unique': the optical filter isolates the channel; ux, uy are consumed
+                for src in (ux, uy):
+                    self.lib.call("plx_filter_apply_dev", self.chfilt, src.data_ptr(), F, st)
             for pol, src in enumerate((ux, uy)):   # rx[f][pol][i] = scale * u_pol[f][i*half]
                 self.lib.call("plx_pick_dev", src.data_ptr(), rx.data_ptr() + pol * self.Lrx * 16, cfg.nfft, self.Lrx, 0,
                               half, self.rx_scale, F, 2 * self.Lrx, st)
@@ -413,12 +508,18 @@ class HotPath:
         if self.rx_gain is not None and self.front is None:   # launch-power ladder: each frame normalised by its own power
             rx.mul_(self.rx_gain[:F])
         if noise_sigma:
-            sig = np.array([float(noise_sigma)])
-            kt = None
+            kt, nf, ncol = None, F, 1
             if noise_keys is not None:
-                kt = self.torch.as_tensor(np.asarray(list(noise_keys), dtype=np.int64), device=self.dev)
-            # one frame of rx = [X | Y] contiguous: a single-field, single-"polarisation" ampliflat with unit gain
-            self.lib.call("plx_ampliflat_dev", rx.data_ptr(), None, 2 * self.Lrx, 1, F, 1.0, sig.ctypes.data, None,
+                keys = np.asarray(list(noise_keys), dtype=np.int64)
+                if keys.size != Ff:
+                    raise ValueError("noise_keys must hold one key per frame (%d), not %d" % (Ff, keys.size))
+                kt = self.torch.as_tensor(keys, device=self.dev)
+                # one key per FRAME (realisation): the nch channel-frames of a frame are the columns of one ampliflat frame,
+                # so each draws its own stream (the column is a word of the Philox counter) under its realisation's key
+                nf, ncol = Ff, self.nch
+            sig = np.full(ncol, float(noise_sigma))
+            # one channel-frame of rx = [X | Y] contiguous: a single-"polarisation" ampliflat column with unit gain
+            self.lib.call("plx_ampliflat_dev", rx.data_ptr(), None, 2 * self.Lrx, ncol, nf, 1.0, sig.ctypes.data, None,
                           int(noise_seed or 0) & (2 ** 64 - 1), kt.data_ptr() if kt is not None else None, 1, 0, st)
         if self.dbp is not None:
             sc = self._dbp_sc[:F]
@@ -620,8 +721,9 @@ class McCampaign:
             side = rxs if rxs is self._rx_stream else None
             hp.receive(ux, uy, self.sigma, 20260101, side, idx)   # receiver noise keyed by realisation index
             with torch.cuda.stream(rxs):
-                v = hp.evm(n)              # a continuous per-realisation sample (mc_estimate) beside the error count
-                e = hp.errors(n)
+                ncf = n * hp.nch if hp.unique else n    # a 'unique' comb: a count per channel-frame, [n nch], channels innermost
+                v = hp.evm(ncf)            # a continuous per-realisation sample (mc_estimate) beside the error count
+                e = hp.errors(ncf)
                 if side is not None:
                     ux.record_stream(rxs); uy.record_stream(rxs)
                 done = torch.cuda.Event()
@@ -630,7 +732,8 @@ class McCampaign:
         return out
 
     def collect(self, handle, with_samples=False):
-        """int64 error counts of a launch() handle (and, with_samples, the float64 EVM samples beside them)"""
+        """int64 error counts of a launch() handle (and, with_samples, the float64 EVM samples beside them); with
+        wdm_field='unique' one per channel-frame: [len(indices) * nch], the channels of a realisation side by side"""
         res, smp = [], []
         for e, v, done in handle or []:
             done.synchronize()             # the counts were formed on the receiver's stream
