@@ -10,11 +10,18 @@
 #define COMPACT_THREADS 256       // k_compact: one workgroup
 #define COL_THREADS_MAX 1024      // k_col_fwd / k_col_inv
 #define ROW_THREADS 128           // k_row's smallest workgroup
+#define ROW_PAD(M) ((M) + (M) / 16)                           // an M-point row in LDS, padded: physical(p) = p + (p >> 4)
+#define ROW_LDS(rows, M) ((size_t)((rows) * ROW_PAD(M) + (M) / 2) * sizeof(cplx))   // k_row: its rows, then W_M^k, k < M / 2
 #define ROWR_THREADS 64           // k_row256r / k_rowsm: one-wave workgroups
-#define ROWR_LDS ((4 * 272 + 128 + 48) * sizeof(cplx))        // 20224 B: eight one-wave workgroups per CU
-#define ROWR_LDS_SC ((4 * 272 + 128 + 80) * sizeof(cplx))     // scalar plans: four rows' bk entries (seven workgroups per CU)
+#define ROWR_ROWS (4 * ROW_PAD(256))                          // k_row256r: a wave's four 256-point rows
+#define ROWR_LDS ((ROWR_ROWS + 128 + 48) * sizeof(cplx))      // rows, W_256^k (k < 128), bk entries: 20224 B, eight one-wave workgroups per CU
+#define ROWR_LDS_SC ((ROWR_ROWS + 128 + 80) * sizeof(cplx))   // scalar plans: four rows' bk entries (seven workgroups per CU)
+#define ROWR_LDS_SPLIT (ROWR_LDS - ROWR_ROWS * sizeof(double))   // <true, false, true>: the rows one component at a time
 #define ROWG_THREADS 256          // k_rowreg
-#define ROWG_NTW(M) ((M) <= 1024 ? (M) / 2 : (M) / 8 + 4)
+#define ROWG_NTW(M) ((M) <= 1024 ? (M) / 2 : (M) / 8 + 4)     // twiddles: the half table, or the compact one (W_M^{4k}, k < M / 8, then W_M^0..3)
+// k_row4k: the padded 4096-point row (both of them: <pair>; one component at a time: <., split>), the compact twiddle table,
+// 16 bk entries, the padded W_256 table (160 entries) and the unit-circle table.  (No <pair, split> kernel exists: split only with pair = 0.)
+#define ROW4K_LDS(pair, split) ((size_t)(((pair) ? 2 : 1) * ROW_PAD(4096) + ROWG_NTW(4096) + 16 + 160 + PLX_CTAB) * sizeof(cplx) - ((split) ? ROW_PAD(4096) * sizeof(double) : 0))
 #define ROWG_LDS(M) ((size_t)((ROWG_THREADS / ((M) / 16)) * ((M) + (M) / 16) + ROWG_NTW(M) + 7 * 16 + PLX_CTAB + 17 * (ROWG_THREADS / ((M) / 16))) * sizeof(cplx))
 #define ROWG_LDS_SPLIT(M) (ROWG_LDS(M) - (size_t)((ROWG_THREADS / ((M) / 16)) * ((M) + (M) / 16)) * sizeof(double))
 #define ROWSM_LDS ((size_t)64 * 17 * sizeof(double) + (7 * 16 + PLX_CTAB) * sizeof(cplx))

@@ -6,6 +6,27 @@
 using plxs::FrameCtl;
 using plxs::SsfmArgs;
 
+// One resolved row-pass launch: what launch_row needs besides the arguments and the number of frame-channels FC.  A plan
+// holds one per use, resolved once at creation (resolve_rows, ssfm_plan.hip: one clause per kernel family).
+enum RowFamily { ROW_GENERAL, ROW_SM, ROW_256, ROW_REG, ROW_4K };   // k_row, k_rowsm, k_row256r, k_rowreg, k_row4k
+struct RowPass {
+    plxs::sweep_kernel_t kern = nullptr;
+    RowFamily family = ROW_GENERAL;
+    unsigned threads = 0;          // workgroup size
+    unsigned gx = 0;               // grid.x per frame-channel
+    size_t lds = 0;                // dynamic LDS
+    bool fold = false;             // grid (gx * FC) -- the kernel decodes row, frame-channel (and polarisation) itself -- not (gx, FC)
+    bool single = false;           // dual plan through a one-polarisation kernel: the arguments rewritten to dual = 0, R = 1
+    bool twice = false;            // ... one launch per polarisation (ux = uy on the second) instead of both in one grid
+};
+// Who launches the row pass.  The argument state of each use is fixed, so the kernel is too:
+enum RowUse {
+    ROW_STEP,                      // the step loop: the plan's own pmd and trunk phasor tables, force = 0, no hmul, no umat
+    ROW_TABLE,                     // plx_ssfm_filter_dev with a multiplier table, plx_ssfm_linear_dev: force = 1, pmd = 0, no umat
+    ROW_MATRIX,                    // plx_ssfm_filter_dev with matrix tables (dual plans): force = 1, pmd = 0, umat couples the polarisations
+    ROW_USES
+};
+
 struct plx_ssfm {
     plx_ssfm_desc d;
     int p, p1, p2;
@@ -21,7 +42,7 @@ struct plx_ssfm {
     hipEvent_t ev = nullptr;  // completion of the last read-back of d_ndone
     std::vector<FrameCtl> h_ctl;
     int brf_sets = 0;
-    size_t lds_col = 0, lds_row = 0;
+    size_t lds_col = 0;
     cplx *d_e1 = nullptr, *d_e2 = nullptr;   // per-frame, per-trunk row / column phasors of PMD plans with a linear db1 (k_pmd_tab)
     unsigned long long *d_slots = nullptr;   // slot barrier of the fused column sweep: [launch parity][frame][tile]
     unsigned long long *d_mbox = nullptr;    // [teams][frames + 4] mailboxes of the fused column sweep's teams, then the two claim counters
@@ -35,20 +56,9 @@ struct plx_ssfm {
     double *d_dzlist = nullptr, *d_dzlog = nullptr;   // diagnostics: replayed / logged step sequences
     int dzlist_cap = 0;
     int col_threads = 512;         // workgroup size of k_col_fwd / k_col_inv
-    int row_threads = ROW_THREADS; // workgroup size of k_row
-    int rowr = 0;                  // k_row256r serves the step's row pass
-    int row4k_split = 0;           // k_row4k<false, true>: the same for 4096-point rows
-    int rowsm = 0;                 // k_rowsm<p2> serves it (rows of 32 / 64 / 128 points; dual polarisation without PMD, scalar)
-    int row256_split = 0;          // k_row256r<true, false, true>: the PMD form with tables at three waves per SIMD
-    int rowg_pair_split = 0;       // ... and the PMD form with phasor tables as well (k_rowreg<., true, false, true>)
-    int rowg_split = 0;            // ... with the exchanges split into real and imaginary halves (three workgroups per CU)
-    int rowreg = 0;                // k_rowreg<p2> serves it (dual polarisation, no PMD, rows of 512 / 1024 / 2048 points)
-    cplx *d_tw2c = nullptr, *d_twmid = nullptr;
-    int row_split = 0, rs_threads = 0; // long rows without PMD: one polarisation per workgroup (scalar row pass twice)
-    size_t rs_lds = 0;
+    RowPass row[ROW_USES];         // the row pass of each use
+    cplx *d_tw2c = nullptr, *d_twmid = nullptr;   // k_rowreg's compact twiddle table; k_rowsm's / k_rowreg's mid twiddles
     int tw_compact = 0;            // 4096-point rows: compact twiddle table in d_tw2, register-blocked row pass k_row4k
-    int row_pair4k = 0;            // ... of a PMD-type plan: both polarisations of a row in one workgroup (k_row4k<true>)
-    size_t rs_lds_pair = 0;
     double *h_brf[2] = {nullptr, nullptr}; // pinned staging of the waveplate tables
     hipEvent_t brf_ev[2] = {nullptr, nullptr};
     int brf_slot = 0;
@@ -67,7 +77,8 @@ struct plx_ssfm {
 
 // The linear step x = ifft(fft(x) .* exp(-i betat dz)) on one frame of `base`'s plan (lin_step, fiber.m:771-773) with the
 // step length forced from the launch: the three transform sweeps through the row-pass dispatch of the step loop and the
-// filter (ssfm_plan.hip).  The host-driven adaptive scheme (ssfm_gateway.hip) calls it; a failed launch is PLX_ERR_HIP.
+// filter (ssfm_plan.hip: ROW_TABLE), scalar plans only.  The host-driven adaptive scheme (ssfm_gateway.hip) calls it; a
+// failed launch is PLX_ERR_HIP.
 PLX_HIDDEN int plx_ssfm_linear_dev(plx_ssfm *P, const SsfmArgs &base, cplx *d_x, double dz, hipStream_t st);
 
 static const double kInv2Pi = 0.15915494309189533577;
