@@ -421,6 +421,35 @@ int plx_phase_noise_dev(double *d_ux, double *d_uy, int64_t stride, int64_t pitc
                         int32_t nfc, int nframes, const double *sigma, uint64_t seed, const int64_t *d_keys,
                         int32_t tag, const double *d_phi_in, double *d_phi_out, double *d_work, void *stream);
 
+/* ------------------------------------------------------- PDM-QPSK transmitter --- */
+/* The reference's Tx chain (electricsource 'cosroll' -> qi_modulator -> create_field(..., power 'average')) on random
+ * bits, one independent draw per (frame key, channel): DESIGN.md 8e.  cf = f nfc + c, K = d_keys[f] or f.
+ * Bits: four streams b_s[m], s = 0..3 (X first, X second, Y first, Y second), m < nsymb.  Word group q = m >> 5 is ONE
+ *   Philox-4x32-10 call, counter (lo32(q), hi32(q), c, PLX_PHILOX_TX_DATA), key as plx_phase_noise_dev documents it
+ *   (k0 = lo32(seed ^ K), k1 = hi32(seed) ^ hi32(K * 0x9E3779B97F4A7C15)), returning r0..r3: b_s[m] = (r_s >> (m & 31)) & 1.
+ *   Counter word 3 = 4 is a stream of its own: ASE uses 0, 1 and the lasers 2, 3, so no data bit coincides with a noise draw.
+ * Waveform: el = the cosroll pulse over two slots (2 nt samples); sample n = m nt + j of a stream's drive is
+ *   sigma el[nt + j] + sigma' el[j], sigma = 2 b[m] - 1, sigma' = 2 b[(m + 1) mod nsymb] - 1.  sin(pi/2 .) is odd, so with
+ *   the HOST table drive [2][nt]: drive[0][j] = sin(pi/2 (el[nt+j] + el[j])) (b[m] == b[m+1]), drive[1][j] = sin(pi/2
+ *   (el[nt+j] - el[j])) (a transition, t = 1),
+ *     x[n] = ((a drive[t_0][j]) sigma_0) k_cf + i ((a drive[t_1][j]) sigma_1) k_cf,  y[n] likewise from streams 2, 3,
+ *   a = sqrt(pavg_mw) / sqrt(2).  No transcendental function is evaluated on the device and no sum is formed.
+ * Power (create_field.m:113-124, per realisation): e_t = sum_j drive[t][j]^2 (sequential, host); ntr = the number of
+ *   (s, m) with b_s[m] != b_s[(m + 1) mod nsymb]; avge = 0.5 pavg_mw ((4 nsymb - ntr) e_0 + ntr e_1) / (nsymb nt);
+ *   d_power[cf] = pavg_mw^2 / avge (that realisation's GSTATE.POWER); k_cf = sqrt(d_power[cf] / pavg_mw).  ntr is an integer:
+ *   the value depends neither on the batch nor on a reduction order.
+ * Beside the field: d_pat uint8 [cf][4][nsymb] = b_s[m] (what plx_decide_count_frames_dev reads with stride 4 nsymb), and
+ *   d_pat_dq (may be NULL) of the same shape = pat_decoder(pat, 'dqpsk') of each polarisation's quaternary pattern
+ *   2 first + second: quarter turns g = [0, 1, 3, 2][pat], d = (g[m-1] - g[m]) mod 4 (circular), (u, v) = [(0,0), (0,1),
+ *   (1,1), (1,0)][d], rows 1 - u, 1 - v (what plx_decide_count_dqpsk_dev reads).  Both 8-byte aligned.
+ * d_ux, d_uy: [nframes][nfc][nsymb nt] complex128.  nsymb: power of two in [16, 2^19]; nt: power of two in [2, 64];
+ * nsymb nt in [256, 2^20]; 1 <= nfc <= 64; nframes <= 65535; pavg_mw finite, > 0; drive finite, e_0 > 0.  drive is copied
+ * into the kernels' argument block: no allocation, no copy, no synchronisation, two launches on `stream`.              */
+#define PLX_PHILOX_TX_DATA 4
+int plx_tx_qpsk_dev(double *d_ux, double *d_uy, int64_t nsymb, int32_t nt, int32_t nfc, int nframes, const double *drive,
+                    double pavg_mw, uint64_t seed, const int64_t *d_keys, uint8_t *d_pat, uint8_t *d_pat_dq, double *d_power,
+                    void *stream);
+
 /* ------------------------------------------------------- a WDM comb as one field --- */
 /* create_field('unique') (create_field.m:165-199) in the time domain, and the channel selection of
  * receiver_cohmix.m:104-125 with a per-channel delay taken out.  N = nfft, s_c = shift[c] the carrier offset of channel c in

@@ -22,6 +22,7 @@ PLX_SSFM_XPM_MANAKOV = 2
 PLX_DBP_STREAMED = 1
 PLX_PHASE_TX = 2
 PLX_PHASE_LO = 3
+PLX_PHILOX_TX_DATA = 4
 
 
 class PolmuxError(RuntimeError):
@@ -133,6 +134,7 @@ SIGNATURES = {
     "plx_ampliflat_dev": [_vp, _vp, _i64, _i32, C.c_int, _dbl, _vp, _vp, C.c_uint64, _vp, _i32, _i32, _vp],
     "plx_phase_noise_dev": [_vp, _vp, _i64, _i64, _dbl, _i64, _i32, C.c_int, _vp, C.c_uint64, _vp, _i32, _vp, _vp, _vp,
                             _vp],
+    "plx_tx_qpsk_dev": [_vp, _vp, _i64, _i32, _i32, C.c_int, _vp, _dbl, C.c_uint64, _vp, _vp, _vp, _vp, _vp],
     "plx_wdm_mux_dev": [_vp, _vp, _vp, _vp, _i64, _i32, C.c_int, _vp, _vp],
     "plx_wdm_select_dev": [_vp, _vp, _vp, _vp, _i64, _i32, C.c_int, _vp, _vp, _vp],
     "plx_front_create": [C.POINTER(_vp), C.POINTER(FrontDesc)],

@@ -7,6 +7,8 @@
 //   0, 1  ASE of ampliflat, X / Y polarisation (plx_misc.hip, counter = (sample lo, sample hi, column, pol))
 //   2     transmitter laser phase noise   (plx_phase.hip, counter = (sample lo, sample hi, channel, 2))
 //   3     local-oscillator phase noise    (plx_phase.hip, counter = (sample lo, sample hi, channel, 3))
+//   4     transmitted data, PLX_PHILOX_TX_DATA (plx_tx.hip, counter = (word group lo, word group hi, channel, 4): the four
+//         words are 32 symbols of the four bit streams, no uniforms are formed)
 // Uniforms from one call: u1 = ((r0 << 21) ^ (r1 >> 11) + 0.5) / 2^53, u2 = the same of (r2, r3); Box-Muller gives
 // sqrt(-2 ln u1) * (cos 2 pi u2, sin 2 pi u2).
 #pragma once

@@ -50,7 +50,7 @@ class HotPathConfig:
                  frontend="pick", oftype="gauss", obw=1.9, oord=3, eftype="bessel5", ebw=0.65, eord=4, lopower=0.0,
                  adcbits=5, span_nf_db=None, rx_amp=False, variants=1, nch=1, chspacing=0.4, share_device=False,
                  equaliser="cde", dbp_steps=4, dbp_xi=1.0, tx_linewidth=0.0, lo_linewidth=0.0, decoding="rotation",
-                 xpm_dualpol=None, wdm_field="sepfields", mux_filter=None):
+                 xpm_dualpol=None, wdm_field="sepfields", mux_filter=None, tx_data="debruijn"):
         """frontend: 'pick' = 2-sps sampling supplied by the harness; 'cohmix' = the reference's own
         receiver_cohmix + ADC + decimate chain (RxPdmCohQpsk.m, Run_my_PDM_QPSK.m:52-73 defaults) on the device.
         nspans > 1: every span but the last is followed by an in-line flat amplifier restoring its loss
@@ -92,7 +92,12 @@ class HotPathConfig:
         xpm_dualpol.
         mux_filter: None, or dict(ftype=, bw=, ord=) -- the multiplexer's channel filter, 'unique' only: every Tx waveform
         is band-limited once on the host, ifft(fft(v) myfilter(ftype, FN, 0.5 bw, ord)) (bw two-sided, in symbol rates,
-        like obw), and rescaled to pavg_mw.  None is the reference's create_field: nothing is filtered."""
+        like obw), and rescaled to pavg_mw.  None is the reference's create_field: nothing is filtered.
+        tx_data: 'debruijn' = every frame carries one of `variants` de Bruijn waveforms synthesised once on the host;
+        'random' = every realisation draws its own data on the device (plx_tx_qpsk_dev): make_batch
+        generates the batch's fields, transmitted patterns and per-realisation power, keyed by its data_keys (channel c of a
+        frame is counter word 2), and the receiver normalises each channel-frame by its own power and counts against its own
+        patterns; HotPath.tx_bits_host states any realisation's data on the host.  variants = 1, no mux_filter, nt <= 64."""
         self.__dict__.update(locals())
         del self.__dict__["self"]
 
@@ -121,6 +126,21 @@ def check_wdm_options(cfg):
     return field == "unique"
 
 
+def check_tx_options(cfg):
+    """The raises of HotPathConfig's tx_data (needs no GPU); returns True for the device transmitter ('random')."""
+    td = cfg.tx_data
+    if not isinstance(td, str) or td not in ("debruijn", "random"):
+        raise ValueError("tx_data must be 'debruijn' or 'random'")
+    if td == "random":
+        if int(cfg.variants) != 1:
+            raise ValueError("tx_data='random' draws every frame's data itself: not with variants != 1")
+        if cfg.mux_filter is not None:
+            raise ValueError("tx_data='random' has no multiplexer filter (the host band-limit has no device counterpart): not with mux_filter")
+        if cfg.nt > 64:
+            raise ValueError("tx_data='random' needs nt <= 64 (the drive tables of plx_tx_qpsk_dev)")
+    return td == "random"
+
+
 def wdm_walkoff(shifts, beta2, b30, total_length, symbolrate, dfn, nt):
     """Walk-off of the channels of a 'unique' field after total_length metres: (delay_symbols, delay).  Channel c sits at
     Om_c = -2 pi symbolrate dfn s_c (where plx_wdm_mux_dev put it: on an integer bin, not at its unrounded wavelength);
@@ -143,6 +163,7 @@ class HotPath:
     def __init__(self, cfg, max_frames):
         import torch
         self.unique = check_wdm_options(cfg)
+        self.random = check_tx_options(cfg)
         if cfg.equaliser not in ("cde", "dbp"):
             raise ValueError("equaliser must be 'cde' or 'dbp'")
         if cfg.equaliser == "dbp" and cfg.frontend != "pick":
@@ -218,6 +239,11 @@ class HotPath:
                 vx, vy = band_limit(vx, vy, hmux, cfg.pavg_mw)
             self.var_host.append((vx, vy, vb))
         self.nvar = len(self.var_host)
+        self.per_frame = self.nvar > 1 or self.random    # every channel-frame is counted against its own patterns
+        if self.random:                                  # the device transmitter: its tables; make_batch fills the rest
+            self.tx_drive = synth.qpsk_drive_tables(cfg.nt)
+            self.pat_frames = self.dpat_frames = self.tx_power = None
+        self._batch = []                                 # the current batch's own tensors (patterns, power, gain)
         if self.nvar > 1:
             self.tx_var = torch.from_numpy(np.stack([np.stack([v[0], v[1]]) for v in self.var_host])).to(self.dev)   # [V, 2, n]
             pv = np.stack([np.ascontiguousarray(v[2].T.astype(np.uint8)) for v in self.var_host])               # [V, 4, nsymb]
@@ -318,15 +344,22 @@ class HotPath:
             self.front = None
 
     # ------------------------------------------------------------------ inputs ---
-    def make_batch(self, nframes, launch_scale=None):
+    def make_batch(self, nframes, launch_scale=None, data_keys=None):
         """Synthetic inputs -> (ux, uy), each [F, n] complex128 ([F, nch, n] for 'sepfields' WDM frames): channel c of
         frame f carries Tx waveform (f nch + c) % variants, with an optional per-frame launch-power scaling (power sweep;
         the receiver then normalises each frame by its own launch power, as a per-run GSTATE.POWER does in
-        DspPdmCohQpsk.m:22-23)."""
+        DspPdmCohQpsk.m:22-23).
+        tx_data='random': one plx_tx_qpsk_dev call draws the data of frame f under data_keys[f] (the frame index when
+        None) and fills, beside the fields, NEW tensors self.pat_frames, self.dpat_frames [F nch, 4, nsymb] and self.tx_power
+        [F nch] -- the current batch's; rx_gain = sqrt(power_mw / tx_power) is formed on the device.  Nothing is read back.
+        A caller that runs the receiver on another stream record_stream()s batch_tensors() there, as it does ux, uy."""
         torch = self.torch
         nch, n = self.nch, self.cfg.nfft
         ncf = nframes * nch
-        if self.nvar > 1:
+        self._batch = []
+        if self.random:
+            ux, uy = self._tx_random(nframes, data_keys)
+        elif self.nvar > 1:
             idx = torch.arange(ncf, device=self.dev) % self.nvar
             ux = self.tx_var[idx, 0].contiguous()
             uy = self.tx_var[idx, 1].contiguous()
@@ -334,14 +367,52 @@ class HotPath:
             ux = self.tx[0].unsqueeze(0).repeat(ncf, 1).contiguous()
             uy = self.tx[1].unsqueeze(0).repeat(ncf, 1).contiguous()
         self.rx_gain = None
+        if self.random:        # each channel-frame normalised by its own power after create_field (its GSTATE.POWER)
+            self.rx_gain = torch.sqrt(self.power_mw / self.tx_power).reshape(-1, 1, 1)
         if launch_scale is not None:
             ls = np.repeat(np.asarray(launch_scale, dtype=float).reshape(-1), nch)
             k = torch.as_tensor(np.sqrt(ls), device=self.dev).reshape(-1, 1)
             ux, uy = ux * k, uy * k
-            self.rx_gain = torch.as_tensor(1.0 / np.sqrt(ls), device=self.dev).reshape(-1, 1, 1)   # per channel-frame
+            g = torch.as_tensor(1.0 / np.sqrt(ls), device=self.dev).reshape(-1, 1, 1)             # per channel-frame
+            self.rx_gain = g if self.rx_gain is None else self.rx_gain * g
+        if self.rx_gain is not None:
+            self._batch.append(self.rx_gain)
         if nch > 1:
             ux, uy = ux.view(nframes, nch, n), uy.view(nframes, nch, n)
         return ux, uy
+
+    def _tx_random(self, nframes, data_keys):
+        """the device transmitter for one batch: fresh fields, patterns and power (never a plan-owned buffer written again:
+        the receiver of the previous batch may still be reading its own on another stream)"""
+        torch = self.torch
+        cfg, nch = self.cfg, self.nch
+        ncf = nframes * nch
+        ux = torch.empty((ncf, cfg.nfft), dtype=torch.complex128, device=self.dev)
+        uy = torch.empty_like(ux)
+        self.pat_frames = torch.empty((ncf, 4, cfg.nsymb), dtype=torch.uint8, device=self.dev)
+        self.dpat_frames = torch.empty_like(self.pat_frames)
+        self.tx_power = torch.empty(ncf, dtype=torch.float64, device=self.dev)
+        kt = None
+        if data_keys is not None:
+            keys = np.asarray(list(data_keys), dtype=np.int64)
+            if keys.size != nframes:
+                raise ValueError("data_keys must hold one key per frame (%d), not %d" % (nframes, keys.size))
+            kt = torch.as_tensor(keys, device=self.dev)
+        self.lib.call("plx_tx_qpsk_dev", ux.data_ptr(), uy.data_ptr(), cfg.nsymb, cfg.nt, nch, nframes,
+                      self.tx_drive.ctypes.data, float(cfg.pavg_mw), 20260101, kt.data_ptr() if kt is not None else None,
+                      self.pat_frames.data_ptr(), self.dpat_frames.data_ptr(), self.tx_power.data_ptr(), self.stream())
+        self._batch += [self.pat_frames, self.dpat_frames, self.tx_power]
+        return ux, uy
+
+    def batch_tensors(self):
+        """the tensors make_batch made for the current batch beside ux, uy (patterns, power, receiver gain)"""
+        return list(self._batch)
+
+    def tx_bits_host(self, keys):
+        """[len(keys), nch, nsymb, 4] uint8: the data tx_data='random' transmits in the realisations `keys` (the host mirror
+        synth.random_qpsk_bits; columns X first, X second, Y first, Y second)"""
+        return np.stack([np.stack([synth.random_qpsk_bits(self.cfg.nsymb, 20260101, int(k), c) for c in range(self.nch)])
+                         for k in keys])
 
     def set_random_pmd(self, seeds):
         """brf draws of fiber.m:274-276, one independent set per frame, keyed by the realisation index alone (a
@@ -444,7 +515,7 @@ class HotPath:
         symbols now in self.sym, differentially decoded and compared with pat_decoder(pat, 'dqpsk') of the transmitted
         patterns after ex20's polarisation-swap rule.  One device call; returns an int64 tensor [F]."""
         out = self.torch.empty(F, dtype=self.torch.int64, device=self.dev)
-        pat, stride = (self.dpat_frames, 4 * self.cfg.nsymb) if self.nvar > 1 else (self.dpat, 0)
+        pat, stride = (self.dpat_frames, 4 * self.cfg.nsymb) if self.per_frame else (self.dpat, 0)
         self.lib.call("plx_decide_count_dqpsk_dev", self.sym.data_ptr(), self.cfg.nsymb, 2, F, pat.data_ptr(), stride,
                       out.data_ptr(), self.stream())
         return out
@@ -530,7 +601,7 @@ class HotPath:
         else:
             self.lib.call("plx_cde_apply_dev", self.cde, rx.data_ptr(), self.eq.data_ptr(), self.Lrx, 2 * F, st)
         self.lib.call("plx_dsp_run_dev", self.dsp, self.eq.data_ptr(), self.sym.data_ptr(), F, st)
-        if self.nvar > 1:     # frames carry different sequences: each compares with its own transmitted bits
+        if self.per_frame:    # frames carry different sequences: each compares with its own transmitted bits
             self.lib.call("plx_decide_count_frames_dev", self.sym.data_ptr(), cfg.nsymb, 2, F, self.pat_frames.data_ptr(),
                           4 * cfg.nsymb, None, self.err.data_ptr(), st)
         else:
@@ -541,7 +612,7 @@ class HotPath:
     def _count_errors(self, F, swap):
         """err [F, 2] of the symbols now in self.sym against the transmitted bits (tributaries exchanged if swap)."""
         torch = self.torch
-        if self.nvar > 1:
+        if self.per_frame:
             pat = self.pat_frames[:F]
             if swap:
                 pat = torch.cat([pat[:, 2:], pat[:, :2]], 1).contiguous()
@@ -707,7 +778,7 @@ class McCampaign:
             n = len(idx)
             if hp.pmd:
                 hp.set_random_pmd(idx)
-            ux, uy = hp.make_batch(n)
+            ux, uy = hp.make_batch(n, data_keys=idx)
             inj = None
             if self.noise_provider is not None:
                 inj = [torch.from_numpy(np.ascontiguousarray(self.noise_provider(idx))).to(hp.dev)]
@@ -726,6 +797,8 @@ class McCampaign:
                 e = hp.errors(ncf)
                 if side is not None:
                     ux.record_stream(rxs); uy.record_stream(rxs)
+                    for t in hp.batch_tensors():      # this batch's patterns, power and gain: the next batch makes its own
+                        t.record_stream(rxs)
                 done = torch.cuda.Event()
                 done.record(rxs)
             out.append((e, v, done))

@@ -123,6 +123,46 @@ def pdm_qpsk_field(nsymb, nt, pavg_mw, seed_x=2, seed_y=3):
     return sx * k, sy * k, bits, pavg_mw * pavg_mw / avge
 
 
+# ------------------------------------------- the device transmitter's host side ---
+def qpsk_drive_tables(nt, duty=1.0, roll=0.2):
+    """[2, nt] float64, the two magnitudes a QPSK drive takes at sample j of a symbol slot after the modulator's
+    sin(pi/2 .): row 0 where b[m] == b[m + 1], sin(pi/2 (el[nt + j] + el[j])); row 1 at a transition,
+    sin(pi/2 (el[nt + j] - el[j])).  With the signs 2 b - 1 this reproduces electricsource_qpsk + qi_modulator bit for
+    bit (plx_tx_qpsk_dev's `drive`)."""
+    el = _pulse_cosroll(roll, duty, nt)
+    return np.ascontiguousarray(np.stack([np.sin(0.5 * np.pi * (el[nt:] + el[:nt])), np.sin(0.5 * np.pi * (el[nt:] - el[:nt]))]))
+
+
+_M32 = np.uint64(0xFFFFFFFF)
+PHILOX_TX_DATA = 4
+
+
+def _philox4x32(c0, c1, c2, c3, k0, k1):
+    """Philox-4x32-10 on uint64 arrays holding 32-bit words (csrc/plx_philox.h)"""
+    c = [np.asarray(x, dtype=np.uint64) & _M32 for x in (c0, c1, c2, c3)]
+    k0, k1 = np.uint64(k0) & _M32, np.uint64(k1) & _M32
+    for _ in range(10):
+        p0, p1 = np.uint64(0xD2511F53) * c[0], np.uint64(0xCD9E8D57) * c[2]
+        c = [((p1 >> np.uint64(32)) ^ c[1] ^ k0) & _M32, p1 & _M32, ((p0 >> np.uint64(32)) ^ c[3] ^ k1) & _M32, p0 & _M32]
+        k0, k1 = (k0 + np.uint64(0x9E3779B9)) & _M32, (k1 + np.uint64(0xBB67AE85)) & _M32
+    return c
+
+
+def random_qpsk_bits(nsymb, seed, key, chan):
+    """[nsymb, 4] uint8 (X first, X second, Y first, Y second): the data plx_tx_qpsk_dev gives channel `chan` of the
+    realisation `key` under `seed` -- word group q = m >> 5 is one Philox call with counter (lo32(q), hi32(q), chan, 4) and
+    the library's key derivation; b_s[m] = (r_s >> (m & 31)) & 1 (include/polmux_hip.h)."""
+    with np.errstate(over="ignore"):
+        seed, key = np.uint64(int(seed) & (2 ** 64 - 1)), np.uint64(int(key) & (2 ** 64 - 1))
+        k0 = (seed ^ key) & _M32
+        k1 = ((seed >> np.uint64(32)) ^ ((key * np.uint64(0x9E3779B97F4A7C15)) >> np.uint64(32))) & _M32
+    m = np.arange(nsymb, dtype=np.uint64)
+    q = np.arange(-(-nsymb // 32), dtype=np.uint64)
+    r = _philox4x32(q & _M32, q >> np.uint64(32), np.full(q.size, chan, np.uint64), np.full(q.size, PHILOX_TX_DATA, np.uint64), k0, k1)
+    sh = m & np.uint64(31)
+    return np.stack([(w[(m >> np.uint64(5)).astype(np.int64)] >> sh) & np.uint64(1) for w in r], 1).astype(np.uint8)
+
+
 # --------------------------------------------------------------- fiber.m tables ---
 CLIGHT = 299792458.0                                    # reset_all.m:105
 
