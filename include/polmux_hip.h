@@ -513,6 +513,24 @@ int plx_filter_create(plx_filter **plan, int64_t nfft, int max_signals, const do
 int plx_filter_destroy(plx_filter *plan);
 int plx_filter_apply_dev(plx_filter *plan, double *d_x, int nsignals, void *stream);
 
+/* The transmitter's channel filter with its power normalisation: band-limit npairs (X, Y) row pairs with the
+ * plan's H and bring every pair back to the average power pavg_mw, on the device and per pair.
+ *   plan: plx_filter_create(nfft, max_signals >= npairs, h_re, h_im); d_ux, d_uy: [npairs][nfft] complex128, in place.
+ *   For pair p: x_p = ifft(fft(x_p) H), y_p likewise (exactly plx_filter_apply_dev on those rows);
+ *   m_p = (1 / nfft) sum_n (|x_p[n]|^2 + |y_p[n]|^2); k_p = sqrt(pavg_mw / m_p); both rows *= k_p; d_gain[p] = k_p
+ *   (d_gain may be NULL).  If m_p is not finite or not > 0 (H removed everything), or k_p is not finite, the rows stay as
+ *   filtered and d_gain[p] = 0: no NaN is manufactured.
+ * The sum has a FIXED order that depends on nfft alone: tiles of 2048 samples, one partial per tile in
+ * d_work[p * ntiles + t] (ntiles = ceil(nfft / 2048) <= 512), every partial formed in the same in-workgroup order, and the
+ * partials of a pair added in the same order by every workgroup that scales one of its tiles.  No floating-point atomics:
+ * a pair's result does not depend on npairs or on its place in the batch, bit for bit.
+ * Two launches behind the two filter passes, all on `stream`; no allocation, no copy, no synchronisation.  The (pair,
+ * tile) items are strided over by a one-dimensional grid of at most 2048 workgroups: npairs is bounded by the plan alone.
+ * d_work: npairs * ceil(nfft / 2048) doubles, the caller's.
+ * PLX_ERR_ARG: plan, d_ux, d_uy or d_work NULL; npairs outside [1, max_signals]; pavg_mw not finite or not > 0. */
+int plx_tx_bandlimit_dev(plx_filter *plan, double *d_ux, double *d_uy, int npairs, double pavg_mw, double *d_gain,
+                         double *d_work, void *stream);
+
 /* ------------------------------------------------------------------ inverse PMD --- */
 /* inverse_pmd(brf, options)  inverse_pmd.m:91-145: the per-frequency PMD matrix U of a link of `nfibers` fibres
  * (brf{n} as returned by fiber), Uinv = U^H, and its application to a unique dual-polarisation field.

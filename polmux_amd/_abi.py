@@ -146,6 +146,7 @@ SIGNATURES = {
     "plx_filter_create": [C.POINTER(_vp), _i64, C.c_int, _vp, _vp],
     "plx_filter_destroy": [_vp],
     "plx_filter_apply_dev": [_vp, _vp, C.c_int, _vp],
+    "plx_tx_bandlimit_dev": [_vp, _vp, _vp, C.c_int, _dbl, _vp, _vp, _vp],
     "plx_pmdinv_create": [C.POINTER(_vp), _i64, C.c_int],
     "plx_pmdinv_destroy": [_vp],
     "plx_pmdinv_set_link": [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int],

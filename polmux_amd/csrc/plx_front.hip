@@ -263,12 +263,7 @@ extern "C" int plx_front_run_dev(plx_front *P, double *d_ux, double *d_uy, int n
 // y = ifft(fft(x) .* H) on [nsig][nfft] complex128 signals (every row filtered by the same H): the DSP-side
 // dispersion-compensating FIR of RxPdmCohQpsk.m:74-84 / dsp4cohdec.m:163-173 (H from DispCompFilter, host) and any
 // other fixed frequency response a caller wants applied on the device.
-struct plx_filter {
-    plx_ssfm *fft = nullptr;
-    cplx *d_h = nullptr;
-    int max_sig = 0;
-};
-
+// (struct plx_filter: plx_internal.h -- plx_txfilt.hip runs the same plan)
 extern "C" int plx_filter_create(plx_filter **out, int64_t nfft, int max_signals, const double *h_re, const double *h_im)
 {
     if (!out || !h_re) PLX_FAIL(PLX_ERR_ARG, "plx_filter_create: null argument");

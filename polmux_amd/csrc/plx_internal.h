@@ -16,3 +16,11 @@ PLX_HIDDEN int plx_ssfm_filter_dev(plx_ssfm *P, cplx *d_ux, cplx *d_uy, const cp
                                    const cplx *d_umat = nullptr);
 // natural frequency index k of row-pass position pos (and the plan's N), for kernels that fill such tables
 PLX_HIDDEN void plx_ssfm_geometry(const plx_ssfm *P, int *p1, int *p2);
+
+// The plan of plx_filter_* (plx_front.hip): the FFT engine of a one-column, single-polarisation SSFM plan for max_sig
+// rows, and the response H in the order its row pass visits the spectrum.  plx_txfilt.hip applies it to (X, Y) pairs.
+struct plx_filter {
+    plx_ssfm *fft = nullptr;
+    cplx *d_h = nullptr;
+    int max_sig = 0;
+};

@@ -50,7 +50,8 @@ class HotPathConfig:
                  frontend="pick", oftype="gauss", obw=1.9, oord=3, eftype="bessel5", ebw=0.65, eord=4, lopower=0.0,
                  adcbits=5, span_nf_db=None, rx_amp=False, variants=1, nch=1, chspacing=0.4, share_device=False,
                  equaliser="cde", dbp_steps=4, dbp_xi=1.0, tx_linewidth=0.0, lo_linewidth=0.0, decoding="rotation",
-                 xpm_dualpol=None, wdm_field="sepfields", mux_filter=None, tx_data="debruijn"):
+                 xpm_dualpol=None, wdm_field="sepfields", mux_filter=None, tx_data="debruijn",
+                 tx_filter=None):
         """frontend: 'pick' = 2-sps sampling supplied by the harness; 'cohmix' = the reference's own
         receiver_cohmix + ADC + decimate chain (RxPdmCohQpsk.m, Run_my_PDM_QPSK.m:52-73 defaults) on the device.
         nspans > 1: every span but the last is followed by an in-line flat amplifier restoring its loss
@@ -97,7 +98,14 @@ class HotPathConfig:
         'random' = every realisation draws its own data on the device (plx_tx_qpsk_dev): make_batch
         generates the batch's fields, transmitted patterns and per-realisation power, keyed by its data_keys (channel c of a
         frame is counter word 2), and the receiver normalises each channel-frame by its own power and counts against its own
-        patterns; HotPath.tx_bits_host states any realisation's data on the host.  variants = 1, no mux_filter, nt <= 64."""
+        patterns; HotPath.tx_bits_host states any realisation's data on the host.  variants = 1, no mux_filter, nt <= 64.
+        tx_filter: None, or dict(ftype=, bw=[, ord=]) -- the transmitter's channel filter on the DEVICE (plx_tx_bandlimit_dev,
+        DESIGN.md section 8f), with both tx_data and both wdm_field values and any nch: every channel-frame is band-limited,
+        ifft(fft(v) myfilter(ftype, FN, 0.5 bw, ord)) (bw two-sided, in symbol rates: mux_filter's table), and rescaled to
+        pavg_mw by its OWN mean power.  tx_data='random': on every batch, behind plx_tx_qpsk_dev on make_batch's stream and
+        with no read-back; 'debruijn': on the `variants` waveforms once, when the plan is made.  The patterns, tx_power,
+        rx_gain and power_mw are what they are without the filter.  Not together with mux_filter (the host route).  None:
+        nothing is launched."""
         self.__dict__.update(locals())
         del self.__dict__["self"]
 
@@ -126,6 +134,26 @@ def check_wdm_options(cfg):
     return field == "unique"
 
 
+def check_tx_filter(cfg):
+    """The raises of HotPathConfig's tx_filter (needs no GPU); returns True when the device band-limit is asked for."""
+    tf = cfg.tx_filter
+    if tf is None:
+        return False
+    if not isinstance(tf, dict) or "ftype" not in tf or "bw" not in tf or set(tf) - {"ftype", "bw", "ord"}:
+        raise ValueError("tx_filter must be None or dict(ftype=..., bw=...[, ord=...])")
+    try:
+        bw = float(tf["bw"]) if np.ndim(tf["bw"]) == 0 and not isinstance(tf["bw"], (bool, str, bytes)) else math.nan
+    except (TypeError, ValueError):
+        bw = math.nan
+    if not (math.isfinite(bw) and bw > 0):
+        raise ValueError("tx_filter: bw must be a finite scalar > 0 (two-sided, in symbol rates)")
+    if not isinstance(tf["ftype"], str):
+        raise ValueError("tx_filter: ftype must be a filter name of myfilter")
+    if cfg.mux_filter is not None:
+        raise ValueError("tx_filter is the device route of the channel filter and mux_filter the host route: not both")
+    return True
+
+
 def check_tx_options(cfg):
     """The raises of HotPathConfig's tx_data (needs no GPU); returns True for the device transmitter ('random')."""
     td = cfg.tx_data
@@ -135,7 +163,8 @@ def check_tx_options(cfg):
         if int(cfg.variants) != 1:
             raise ValueError("tx_data='random' draws every frame's data itself: not with variants != 1")
         if cfg.mux_filter is not None:
-            raise ValueError("tx_data='random' has no multiplexer filter (the host band-limit has no device counterpart): not with mux_filter")
+            raise ValueError("tx_data='random' has no multiplexer filter (mux_filter is the host band-limit; tx_filter is the device one): "
+                             "not with mux_filter")
         if cfg.nt > 64:
             raise ValueError("tx_data='random' needs nt <= 64 (the drive tables of plx_tx_qpsk_dev)")
     return td == "random"
@@ -164,6 +193,7 @@ class HotPath:
         import torch
         self.unique = check_wdm_options(cfg)
         self.random = check_tx_options(cfg)
+        self.txfilt_on = check_tx_filter(cfg)
         if cfg.equaliser not in ("cde", "dbp"):
             raise ValueError("equaliser must be 'cde' or 'dbp'")
         if cfg.equaliser == "dbp" and cfg.frontend != "pick":
@@ -223,11 +253,9 @@ class HotPath:
             from .rxfront import myfilter
             hmux = myfilter(mf["ftype"], GSTATE.FN, 0.5 * float(mf["bw"]), mf.get("ord"))
             ux, uy = band_limit(ux, uy, hmux, cfg.pavg_mw)
-        self.tx_host = (ux, uy)
         self.bits = bits
         self.power_mw = power
         GSTATE.POWER = np.full(nch, power)
-        self.tx = torch.from_numpy(np.stack([ux, uy])).to(self.dev)          # [2, n]
         self.pat = torch.from_numpy(np.ascontiguousarray(bits.T.astype(np.uint8))).to(self.dev)   # [4, nsymb]
         # further Tx waveforms (other de Bruijn seeds): heterogeneous batches whose frames differ in data
         self.var_host = [(ux, uy, bits)]
@@ -239,6 +267,29 @@ class HotPath:
                 vx, vy = band_limit(vx, vy, hmux, cfg.pavg_mw)
             self.var_host.append((vx, vy, vb))
         self.nvar = len(self.var_host)
+        self.txfilt = self._txfilt_work = self.tx_gain = None
+        if self.txfilt_on:                               # the transmitter's channel filter (device)
+            from .rxfront import myfilter
+            tf = cfg.tx_filter
+            htx = np.asarray(myfilter(tf["ftype"], GSTATE.FN, 0.5 * float(tf["bw"]), tf.get("ord")), dtype=complex)
+            hr, hi = np.ascontiguousarray(htx.real), np.ascontiguousarray(htx.imag)
+            npairs = self.CF if self.random else self.nvar
+            self.txfilt = C.c_void_p()
+            self.lib.call("plx_filter_create", C.byref(self.txfilt), n, npairs, hr.ctypes.data, hi.ctypes.data)
+            # tile partials of the power sum: the plan's, touched only on the stream make_batch runs on
+            self._txfilt_work = torch.empty(npairs * (-(-n // 2048)), dtype=torch.float64, device=self.dev)
+            if not self.random:                          # the V waveforms, once: tx_host / var_host hold what is read back
+                dx = torch.from_numpy(np.stack([v[0] for v in self.var_host])).to(self.dev)
+                dy = torch.from_numpy(np.stack([v[1] for v in self.var_host])).to(self.dev)
+                self.lib.call("plx_tx_bandlimit_dev", self.txfilt, dx.data_ptr(), dy.data_ptr(), self.nvar, float(cfg.pavg_mw),
+                              None, self._txfilt_work.data_ptr(), self.stream())
+                hx, hy = dx.cpu().numpy(), dy.cpu().numpy()
+                self.var_host = [(hx[v], hy[v], self.var_host[v][2]) for v in range(self.nvar)]
+                ux, uy = self.var_host[0][:2]
+                self.lib.call("plx_filter_destroy", self.txfilt)
+                self.txfilt = self._txfilt_work = None
+        self.tx_host = (ux, uy)
+        self.tx = torch.from_numpy(np.stack([ux, uy])).to(self.dev)          # [2, n]
         self.per_frame = self.nvar > 1 or self.random    # every channel-frame is counted against its own patterns
         if self.random:                                  # the device transmitter: its tables; make_batch fills the rest
             self.tx_drive = synth.qpsk_drive_tables(cfg.nt)
@@ -332,10 +383,10 @@ class HotPath:
 
     def close(self):
         for name, h in (("plx_ssfm_destroy", self.ssfm), ("plx_cde_destroy", self.cde), ("plx_dsp_destroy", self.dsp),
-                        ("plx_filter_destroy", self.chfilt)):
+                        ("plx_filter_destroy", self.chfilt), ("plx_filter_destroy", self.txfilt)):
             if h:
                 self.lib.call(name, h)
-        self.ssfm = self.cde = self.dsp = self.chfilt = None
+        self.ssfm = self.cde = self.dsp = self.chfilt = self.txfilt = None
         if self.dbp is not None:
             self.dbp.close()
             self.dbp = None
@@ -352,6 +403,8 @@ class HotPath:
         tx_data='random': one plx_tx_qpsk_dev call draws the data of frame f under data_keys[f] (the frame index when
         None) and fills, beside the fields, NEW tensors self.pat_frames, self.dpat_frames [F nch, 4, nsymb] and self.tx_power
         [F nch] -- the current batch's; rx_gain = sqrt(power_mw / tx_power) is formed on the device.  Nothing is read back.
+        With tx_filter the same call is followed by plx_tx_bandlimit_dev on the F nch pairs (before any launch_scale), which
+        leaves its gains in a NEW tensor self.tx_gain [F nch].
         A caller that runs the receiver on another stream record_stream()s batch_tensors() there, as it does ux, uy."""
         torch = self.torch
         nch, n = self.nch, self.cfg.nfft
@@ -402,6 +455,11 @@ class HotPath:
                       self.tx_drive.ctypes.data, float(cfg.pavg_mw), 20260101, kt.data_ptr() if kt is not None else None,
                       self.pat_frames.data_ptr(), self.dpat_frames.data_ptr(), self.tx_power.data_ptr(), self.stream())
         self._batch += [self.pat_frames, self.dpat_frames, self.tx_power]
+        if self.txfilt:        # band-limit every channel-frame and bring it back to pavg_mw by its own mean power
+            self.tx_gain = torch.empty(ncf, dtype=torch.float64, device=self.dev)
+            self.lib.call("plx_tx_bandlimit_dev", self.txfilt, ux.data_ptr(), uy.data_ptr(), ncf, float(cfg.pavg_mw),
+                          self.tx_gain.data_ptr(), self._txfilt_work.data_ptr(), self.stream())
+            self._batch.append(self.tx_gain)
         return ux, uy
 
     def batch_tensors(self):
