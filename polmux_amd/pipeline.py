@@ -14,9 +14,13 @@ import math
 import numpy as np
 
 from . import _abi, synth
+from .ampliflat import ase_sigma
 from .fiber import fiber_tables, parse_flag
-from .gstate import GSTATE
+from .gstate import GSTATE, unique_field_shifts
 from .rx import cde_transfer, dsp_params_struct
+from .rxfront import myfilter
+
+MASTER_SEED = 20260101      # of every counter-based generator: data, birefringence, ASE, laser phase, receiver noise
 
 
 def dqpsk_expected(bits):
@@ -114,16 +118,27 @@ class HotPathConfig:
         return self.nsymb * self.nt
 
 
+def _check_filter(name, f):
+    """the raises of a channel-filter option `name` = dict(ftype=, bw=[, ord=]) (mux_filter, tx_filter)"""
+    if not isinstance(f, dict) or "ftype" not in f or "bw" not in f or set(f) - {"ftype", "bw", "ord"}:
+        raise ValueError("%s must be None or dict(ftype=..., bw=...[, ord=...])" % name)
+    try:
+        bw = float(f["bw"]) if np.ndim(f["bw"]) == 0 and not isinstance(f["bw"], (bool, str, bytes)) else math.nan
+    except (TypeError, ValueError):
+        bw = math.nan
+    if not (math.isfinite(bw) and bw > 0):
+        raise ValueError("%s: bw must be a finite scalar > 0 (two-sided, in symbol rates)" % name)
+    if not isinstance(f["ftype"], str):
+        raise ValueError("%s: ftype must be a filter name of myfilter" % name)
+
+
 def check_wdm_options(cfg):
     """The raises of HotPathConfig's wdm_field / mux_filter (needs no GPU); returns True for a 'unique' field."""
     field, mf = cfg.wdm_field, cfg.mux_filter
     if not isinstance(field, str) or field not in ("sepfields", "unique"):
         raise ValueError("wdm_field must be 'sepfields' or 'unique'")
     if mf is not None:
-        if not isinstance(mf, dict) or "ftype" not in mf or "bw" not in mf or set(mf) - {"ftype", "bw", "ord"}:
-            raise ValueError("mux_filter must be None or dict(ftype=..., bw=...[, ord=...])")
-        if not (np.ndim(mf["bw"]) == 0 and math.isfinite(float(mf["bw"])) and float(mf["bw"]) > 0):
-            raise ValueError("mux_filter: bw must be a finite scalar > 0 (two-sided, in symbol rates)")
+        _check_filter("mux_filter", mf)
         if field == "sepfields":
             raise ValueError("mux_filter needs wdm_field='unique' (it would change the 'sepfields' frames)")
     if field == "unique":
@@ -136,19 +151,9 @@ def check_wdm_options(cfg):
 
 def check_tx_filter(cfg):
     """The raises of HotPathConfig's tx_filter (needs no GPU); returns True when the device band-limit is asked for."""
-    tf = cfg.tx_filter
-    if tf is None:
+    if cfg.tx_filter is None:
         return False
-    if not isinstance(tf, dict) or "ftype" not in tf or "bw" not in tf or set(tf) - {"ftype", "bw", "ord"}:
-        raise ValueError("tx_filter must be None or dict(ftype=..., bw=...[, ord=...])")
-    try:
-        bw = float(tf["bw"]) if np.ndim(tf["bw"]) == 0 and not isinstance(tf["bw"], (bool, str, bytes)) else math.nan
-    except (TypeError, ValueError):
-        bw = math.nan
-    if not (math.isfinite(bw) and bw > 0):
-        raise ValueError("tx_filter: bw must be a finite scalar > 0 (two-sided, in symbol rates)")
-    if not isinstance(tf["ftype"], str):
-        raise ValueError("tx_filter: ftype must be a filter name of myfilter")
+    _check_filter("tx_filter", cfg.tx_filter)
     if cfg.mux_filter is not None:
         raise ValueError("tx_filter is the device route of the channel filter and mux_filter the host route: not both")
     return True
@@ -168,6 +173,38 @@ def check_tx_options(cfg):
         if cfg.nt > 64:
             raise ValueError("tx_data='random' needs nt <= 64 (the drive tables of plx_tx_qpsk_dev)")
     return td == "random"
+
+
+def check_config(cfg):
+    """Every raise of HotPathConfig's options (needs no GPU, no library, no torch); returns (unique, random, txfilt_on)."""
+    unique, random, txfilt_on = check_wdm_options(cfg), check_tx_options(cfg), check_tx_filter(cfg)
+    if cfg.equaliser not in ("cde", "dbp"):
+        raise ValueError("equaliser must be 'cde' or 'dbp'")
+    if cfg.equaliser == "dbp" and cfg.frontend != "pick":
+        raise ValueError("equaliser='dbp' needs frontend='pick' (the cohmix LO/ADC chain is not proportional to the field)")
+    for name in ("tx_linewidth", "lo_linewidth"):
+        v = getattr(cfg, name)
+        if not (np.ndim(v) == 0 and math.isfinite(float(v)) and float(v) >= 0):
+            raise ValueError("%s must be a finite scalar >= 0 (normalised to the symbol rate)" % name)
+    if cfg.decoding not in ("rotation", "dqpsk"):
+        raise ValueError("decoding must be 'rotation' or 'dqpsk'")
+    if cfg.xpm_dualpol not in (None, "manakov"):
+        raise ValueError("xpm_dualpol must be None or 'manakov'")
+    if cfg.xpm_dualpol and cfg.equaliser == "dbp":
+        raise ValueError("equaliser='dbp' has no XPM backpropagation: not with xpm_dualpol")
+    if cfg.frontend not in ("pick", "cohmix"):
+        raise ValueError("frontend must be 'pick' or 'cohmix'")
+    return unique, random, txfilt_on
+
+
+def frame_keys(keys, nframes, what):
+    """None, or the keys as a contiguous int64 array of exactly nframes entries (the kernels read keys[f] of every frame)"""
+    if keys is None:
+        return None
+    k = np.ascontiguousarray(keys if isinstance(keys, np.ndarray) else list(keys), dtype=np.int64).reshape(-1)
+    if k.size != nframes:
+        raise ValueError("%s must hold one key per frame (%d), not %d" % (what, nframes, k.size))
+    return k
 
 
 def wdm_walkoff(shifts, beta2, b30, total_length, symbolrate, dfn, nt):
@@ -190,48 +227,52 @@ def band_limit(vx, vy, h, pavg_mw):
 
 class HotPath:
     def __init__(self, cfg, max_frames):
-        import torch
-        self.unique = check_wdm_options(cfg)
-        self.random = check_tx_options(cfg)
-        self.txfilt_on = check_tx_filter(cfg)
-        if cfg.equaliser not in ("cde", "dbp"):
-            raise ValueError("equaliser must be 'cde' or 'dbp'")
-        if cfg.equaliser == "dbp" and cfg.frontend != "pick":
-            raise ValueError("equaliser='dbp' needs frontend='pick' (the cohmix LO/ADC chain is not proportional to the field)")
-        for name in ("tx_linewidth", "lo_linewidth"):
-            v = getattr(cfg, name)
-            if not (np.ndim(v) == 0 and math.isfinite(float(v)) and float(v) >= 0):
-                raise ValueError("%s must be a finite scalar >= 0 (normalised to the symbol rate)" % name)
-        if cfg.decoding not in ("rotation", "dqpsk"):
-            raise ValueError("decoding must be 'rotation' or 'dqpsk'")
-        if cfg.xpm_dualpol not in (None, "manakov"):
-            raise ValueError("xpm_dualpol must be None or 'manakov'")
-        if cfg.xpm_dualpol and cfg.equaliser == "dbp":
-            raise ValueError("equaliser='dbp' has no XPM backpropagation: not with xpm_dualpol")
-        self.torch = torch
+        self.unique, self.random, self.txfilt_on = check_config(cfg)
+        # every handle and optional component, so that close() can run on a half-built plan
+        self.ssfm = self.cde = self.dsp = self.chfilt = self.txfilt = self.dbp = self.front = None
         self.cfg = cfg
         self.F = int(max_frames)
-        self.lib = _abi.get()
-        self.dev = torch.device("cuda", torch.cuda.current_device())
-        n = cfg.nfft
         nch = self.nch = int(cfg.nch)
         self.CF = self.F * nch                           # channel-frames: what the receiver's plans count
-        # --- host side of fiber(): flag, conversions, tables (fiber.m:157-362) ---
-        GSTATE.NSYMB, GSTATE.NT, GSTATE.NCH = cfg.nsymb, cfg.nt, nch
-        GSTATE.SYMBOLRATE = cfg.symbolrate
-        GSTATE.FN = synth.fn_grid(cfg.nsymb, cfg.nt)
-        GSTATE.LAMBDA = cfg.lam + cfg.chspacing * (np.arange(nch) - (nch - 1) / 2)      # lasersource.m: equally spaced comb
+        self.nfc = 1 if self.unique else nch             # columns of the fibre plan: a 'unique' field is one
+        self.power_mw = None                             # (the transmitter sets it, and GSTATE.POWER with it)
+        self.bind_gstate()
+        # --- host side of fiber(): flag, conversions (fiber.m:157-251); the host steps that can still raise ---
         x = {"length": cfg.length, "alphadB": cfg.alphadB, "aeff": cfg.aeff, "n2": cfg.n2, "lambda": cfg.lam,
              "disp": cfg.disp, "slope": cfg.slope, "dphimax": cfg.dphimax, "dzmax": min(cfg.dzmax, cfg.length)}
-        nfc = self.nfc = 1 if self.unique else nch       # columns of the fibre plan: a 'unique' field is one
-        self.fls, dphimaxt, dzmaxt = parse_flag(cfg.flag, nfc, x)
+        self.fls, dphimaxt, dzmaxt = parse_flag(cfg.flag, self.nfc, x)
+        if self.unique:    # the comb as one field: carrier offsets in bins (create_field.m:181-184; raises when NT is too small)
+            self.wdm_shift = np.ascontiguousarray(unique_field_shifts(), dtype=np.int64)
+        import torch
+        self.torch = torch
+        self.lib = _abi.get()
+        self.dev = torch.device("cuda", torch.cuda.current_device())
+        try:
+            t = self._build_fibre(x, dphimaxt, dzmaxt)
+            self._build_tx()
+            self._build_rx(t)
+        except BaseException:
+            self.close()
+            raise
+
+    def _filter_plan(self, h, nsig):
+        """plx_filter_create: a plan that multiplies the spectra of up to nsig signals of nfft samples by the complex table h"""
+        h = np.asarray(h, dtype=complex)
+        hr, hi = np.ascontiguousarray(h.real), np.ascontiguousarray(h.imag)
+        plan = C.c_void_p()
+        self.lib.call("plx_filter_create", C.byref(plan), self.cfg.nfft, nsig, hr.ctypes.data, hi.ctypes.data)
+        return plan
+
+    def _build_fibre(self, x, dphimaxt, dzmaxt):
+        """the fibre plan (fiber.m:274-362: tables, PMD draw); returns fiber_tables' dict"""
+        cfg, nfc = self.cfg, self.nfc
         self.pmd = self.fls[1] == 1
-        nplates = cfg.nplates if self.pmd else 1
+        nplates = self.nplates = cfg.nplates if self.pmd else 1
         dgdrms = math.sqrt(3 * math.pi / 8) * cfg.dgd / math.sqrt(nplates) if self.pmd else 0.0   # fiber.m:277
         t = fiber_tables(x, self.fls, nfc, dgdrms)        # (one column: the centre wavelength lamc and its gamma, as fiber())
         self.alphalin = t["alphalin"]
         d = _abi.SsfmDesc()
-        d.nfft, d.nfc, d.dual_pol, d.max_frames = n, nfc, 1, self.F
+        d.nfft, d.nfc, d.dual_pol, d.max_frames = cfg.nfft, nfc, 1, self.F
         for i in range(4):
             d.fls[i] = self.fls[i]
         d.dzmaxt, d.dphimaxt, d.alphalin, d.length = dzmaxt, dphimaxt, t["alphalin"], cfg.length
@@ -241,43 +282,34 @@ class HotPath:
         self.ssfm = C.c_void_p()
         self.lib.call("plx_ssfm_create_ex", C.byref(self.ssfm), C.byref(d), (_abi.PLX_SSFM_SHARE_DEVICE if cfg.share_device else 0)
                       | (_abi.PLX_SSFM_XPM_MANAKOV if cfg.xpm_dualpol else 0))
-        self.nplates = nplates
         self._profiling = False
         if self.pmd:   # Monte-Carlo style: an independent random birefringence draw per frame (fiber.m:274-276)
             self.set_random_pmd(range(self.F))
-        # --- Tx (host, once): Run_my_PDM_QPSK.m:101-117 ---
-        ux, uy, bits, power = synth.pdm_qpsk_field(cfg.nsymb, cfg.nt, cfg.pavg_mw)
-        hmux = None
-        mf = cfg.mux_filter
-        if mf is not None:                               # the multiplexer's channel filter (host, once per plan)
-            from .rxfront import myfilter
-            hmux = myfilter(mf["ftype"], GSTATE.FN, 0.5 * float(mf["bw"]), mf.get("ord"))
-            ux, uy = band_limit(ux, uy, hmux, cfg.pavg_mw)
-        self.bits = bits
-        self.power_mw = power
-        GSTATE.POWER = np.full(nch, power)
-        self.pat = torch.from_numpy(np.ascontiguousarray(bits.T.astype(np.uint8))).to(self.dev)   # [4, nsymb]
-        # further Tx waveforms (other de Bruijn seeds): heterogeneous batches whose frames differ in data
-        self.var_host = [(ux, uy, bits)]
+        return t
+
+    def _build_tx(self):
+        """the transmitter (host, once: Run_my_PDM_QPSK.m:101-117): waveforms, patterns, the device Tx filter, the drive tables"""
+        torch, cfg, nch = self.torch, self.cfg, self.nch
+        # the default waveform, and further ones (other de Bruijn seeds): heterogeneous batches whose frames differ in data
         maxseed = cfg.nsymb * (cfg.nsymb - 1) // 4
-        for v in range(1, max(1, int(cfg.variants))):
-            vx, vy, vb, vp = synth.pdm_qpsk_field(cfg.nsymb, cfg.nt, cfg.pavg_mw, (2 + 2 * v) % maxseed, (3 + 2 * v) % maxseed)
-            assert abs(vp - power) <= 1e-9 * power      # de Bruijn sequences share their symbol statistics
-            if hmux is not None:
-                vx, vy = band_limit(vx, vy, hmux, cfg.pavg_mw)
-            self.var_host.append((vx, vy, vb))
+        seeds = [()] + [((2 + 2 * v) % maxseed, (3 + 2 * v) % maxseed) for v in range(1, max(1, int(cfg.variants)))]
+        fields = [synth.pdm_qpsk_field(cfg.nsymb, cfg.nt, cfg.pavg_mw, *sd) for sd in seeds]
+        self.bits, self.power_mw = fields[0][2:]
+        assert all(abs(f[3] - self.power_mw) <= 1e-9 * self.power_mw for f in fields)   # de Bruijn sequences share their statistics
+        GSTATE.POWER = np.full(nch, self.power_mw)
+        self.pat = torch.from_numpy(np.ascontiguousarray(self.bits.T.astype(np.uint8))).to(self.dev)   # [4, nsymb]
+        self.var_host = [f[:3] for f in fields]
+        mf, tf = cfg.mux_filter, cfg.tx_filter
+        if mf is not None:                               # the multiplexer's channel filter (host, once per plan)
+            hmux = myfilter(mf["ftype"], GSTATE.FN, 0.5 * float(mf["bw"]), mf.get("ord"))
+            self.var_host = [band_limit(vx, vy, hmux, cfg.pavg_mw) + (vb,) for vx, vy, vb in self.var_host]
         self.nvar = len(self.var_host)
-        self.txfilt = self._txfilt_work = self.tx_gain = None
+        self._txfilt_work = self.tx_gain = None
         if self.txfilt_on:                               # the transmitter's channel filter (device, DESIGN.md section 8f)
-            from .rxfront import myfilter
-            tf = cfg.tx_filter
-            htx = np.asarray(myfilter(tf["ftype"], GSTATE.FN, 0.5 * float(tf["bw"]), tf.get("ord")), dtype=complex)
-            hr, hi = np.ascontiguousarray(htx.real), np.ascontiguousarray(htx.imag)
             npairs = self.CF if self.random else self.nvar
-            self.txfilt = C.c_void_p()
-            self.lib.call("plx_filter_create", C.byref(self.txfilt), n, npairs, hr.ctypes.data, hi.ctypes.data)
+            self.txfilt = self._filter_plan(myfilter(tf["ftype"], GSTATE.FN, 0.5 * float(tf["bw"]), tf.get("ord")), npairs)
             # tile partials of the power sum: the plan's, touched only on the stream make_batch runs on
-            self._txfilt_work = torch.empty(npairs * (-(-n // 2048)), dtype=torch.float64, device=self.dev)
+            self._txfilt_work = torch.empty(npairs * (-(-cfg.nfft // 2048)), dtype=torch.float64, device=self.dev)
             if not self.random:                          # the V waveforms, once: tx_host / var_host hold what is read back
                 dx = torch.from_numpy(np.stack([v[0] for v in self.var_host])).to(self.dev)
                 dy = torch.from_numpy(np.stack([v[1] for v in self.var_host])).to(self.dev)
@@ -285,16 +317,15 @@ class HotPath:
                               None, self._txfilt_work.data_ptr(), self.stream())
                 hx, hy = dx.cpu().numpy(), dy.cpu().numpy()
                 self.var_host = [(hx[v], hy[v], self.var_host[v][2]) for v in range(self.nvar)]
-                ux, uy = self.var_host[0][:2]
                 self.lib.call("plx_filter_destroy", self.txfilt)
                 self.txfilt = self._txfilt_work = None
-        self.tx_host = (ux, uy)
-        self.tx = torch.from_numpy(np.stack([ux, uy])).to(self.dev)          # [2, n]
+        self.tx_host = self.var_host[0][:2]
+        self.tx = torch.from_numpy(np.stack(self.tx_host)).to(self.dev)      # [2, n]
         self.per_frame = self.nvar > 1 or self.random    # every channel-frame is counted against its own patterns
         if self.random:                                  # the device transmitter: its tables; make_batch fills the rest
             self.tx_drive = synth.qpsk_drive_tables(cfg.nt)
             self.pat_frames = self.dpat_frames = self.tx_power = None
-        self._batch = []                                 # the current batch's own tensors (patterns, power, gain)
+        self._batch, self.rx_gain = [], None             # the current batch's own tensors, its per-frame receiver scale (make_batch)
         if self.nvar > 1:
             self.tx_var = torch.from_numpy(np.stack([np.stack([v[0], v[1]]) for v in self.var_host])).to(self.dev)   # [V, 2, n]
             pv = np.stack([np.ascontiguousarray(v[2].T.astype(np.uint8)) for v in self.var_host])               # [V, 4, nsymb]
@@ -304,21 +335,18 @@ class HotPath:
         self.dpat = torch.from_numpy(dv[0]).to(self.dev)
         if self.nvar > 1:
             self.dpat_frames = torch.from_numpy(dv[np.arange(self.CF) % self.nvar].copy()).to(self.dev)
-        if self.unique:
-            # the comb as one field: carrier offsets in bins (create_field.m:181-184; raises when NT is too small for the
-            # comb), the walk-off select takes out, and the plan-owned field the fibre works on
-            from .gstate import unique_field_shifts
-            self.wdm_shift = np.ascontiguousarray(unique_field_shifts(), dtype=np.int64)
+
+    def _build_rx(self, t):
+        """the receiver: a 'unique' comb's walk-off (from fiber_tables' t) and field, CDE / DBP, DSP, front end, buffers"""
+        torch, cfg, nch, n = self.torch, self.cfg, self.nch, self.cfg.nfft
+        if self.unique:    # the walk-off select takes out, and the plan-owned field the fibre works on
             self.wdm_delay_symbols, self.wdm_delay = wdm_walkoff(self.wdm_shift, float(t["beta2"][0]), float(t["b30"]),
                                                                  cfg.nspans * cfg.length, cfg.symbolrate,
                                                                  GSTATE.FN[1] - GSTATE.FN[0], cfg.nt)
-            self.wdm_delay = np.ascontiguousarray(self.wdm_delay)
             self.wx = torch.empty((self.F, n), dtype=torch.complex128, device=self.dev)
             self.wy = torch.empty_like(self.wx)
         self._phase_work = {}                            # tile sums of the phase generator, per laser (allocated on use)
         self._lo_buf = None                              # [F nch, nfft] LO phase of the cohmix route (allocated on use)
-        self.rx_gain = None                              # per-frame receiver scale of a launch-power ladder (make_batch)
-        # --- Rx plans ---
         self.Lrx = 2 * cfg.nsymb
         fs = 2 * cfg.symbolrate * 1e9                                         # Run_my_PDM_QPSK.m:66,149
         N = min(cfg.fft_length, self.Lrx)
@@ -330,13 +358,12 @@ class HotPath:
                    cmaparams=dict(R=[1, 1], mu=cfg.cma_mu, taps=cfg.cma_taps, txpolars=2, phizero=0),
                    easiparams=dict(mu=cfg.cma_mu, txpolars=2, phizero=0), modorder=2, freqavg=cfg.freqavg,
                    phasavg=cfg.phasavg, poworder=cfg.poworder)
-        self.dsp_p = dsp_params_struct(dsp, power)
+        self.dsp_p = dsp_params_struct(dsp, self.power_mw)
         self.dsp = C.c_void_p()
         self.lib.call("plx_dsp_create", C.byref(self.dsp), self.Lrx, 2, self.CF, C.byref(self.dsp_p))
         # receive scale: undo the span loss and bring symbols to the 4*sqrt(P) full scale that
         # DspPdmCohQpsk divides by (DspPdmCohQpsk.m:22-23, "2* -> see receiver_cohmix")
-        self.rx_scale = 4.0 * math.sqrt(power) / math.sqrt(power / 2.0)
-        self.dbp = None
+        self.rx_scale = 4.0 * math.sqrt(self.power_mw) / math.sqrt(self.power_mw / 2.0)
         if cfg.equaliser == "dbp":
             # the 2-sps samples are the field after the receiver's amplifier (physical with rx_amp, else folded into
             # rx_scale below) times this full-scale factor times rx_gain: DBP's scale maps them back to sqrt(mW)
@@ -349,7 +376,6 @@ class HotPath:
             self._dbp_sc = torch.full((self.CF,), self.dbp_scale, dtype=torch.float64, device=self.dev)
         if not cfg.rx_amp:
             self.rx_scale *= math.exp(0.5 * self.alphalin * cfg.length)
-        self.front = None
         if cfg.frontend == "cohmix":
             from . import rxfront
             rp = dict(oftype=cfg.oftype, obw=cfg.obw, oord=cfg.oord, eftype=cfg.eftype, ebw=cfg.ebw, eord=cfg.eord,
@@ -363,22 +389,14 @@ class HotPath:
             self.front_shifts = [rxfront._mround(-delay * cfg.nt)] * 2         # 'theory' delay, RxPdmCohQpsk.m:124-137
             self.front_tables = dict(hopt=hopt, elo=elo, hel=hel, fir=rxfront.fir1_lowpass(16, 1.0 / r), decim=r)
             self.front = rxfront._Front(n, True, self.CF, hopt, elo, hel, True, cfg.adcbits, r, self.front_tables["fir"])
-        elif cfg.frontend != "pick":
-            raise ValueError("frontend must be 'pick' or 'cohmix'")
-        self.chfilt = None
-        if self.unique and nch > 1 and self.front is None:
+        elif self.unique and nch > 1:
             # the pick has no optical filter of its own: a channel-frame cut out of the one field still has its neighbours
             # beside it in the spectrum (one channel has none: nch = 1 is the one-channel path)
-            from .rxfront import myfilter
-            hch = np.asarray(myfilter(cfg.oftype, GSTATE.FN, 0.5 * cfg.obw, cfg.oord), dtype=complex)
-            self.chfilt_h = hch
-            hr, hi = np.ascontiguousarray(hch.real), np.ascontiguousarray(hch.imag)
-            self.chfilt = C.c_void_p()
-            self.lib.call("plx_filter_create", C.byref(self.chfilt), n, self.CF, hr.ctypes.data, hi.ctypes.data)
-        c128 = torch.complex128
-        self.rx = torch.empty((self.CF, 2, self.Lrx), dtype=c128, device=self.dev)
+            self.chfilt_h = np.asarray(myfilter(cfg.oftype, GSTATE.FN, 0.5 * cfg.obw, cfg.oord), dtype=complex)
+            self.chfilt = self._filter_plan(self.chfilt_h, self.CF)
+        self.rx = torch.empty((self.CF, 2, self.Lrx), dtype=torch.complex128, device=self.dev)
         self.eq = torch.empty_like(self.rx)
-        self.sym = torch.empty((self.CF, 2, cfg.nsymb), dtype=c128, device=self.dev)
+        self.sym = torch.empty((self.CF, 2, cfg.nsymb), dtype=torch.complex128, device=self.dev)
         self.err = torch.zeros((self.CF, 2), dtype=torch.int64, device=self.dev)
 
     def close(self):
@@ -419,9 +437,8 @@ class HotPath:
         else:
             ux = self.tx[0].unsqueeze(0).repeat(ncf, 1).contiguous()
             uy = self.tx[1].unsqueeze(0).repeat(ncf, 1).contiguous()
-        self.rx_gain = None
-        if self.random:        # each channel-frame normalised by its own power after create_field (its GSTATE.POWER)
-            self.rx_gain = torch.sqrt(self.power_mw / self.tx_power).reshape(-1, 1, 1)
+        # tx_data='random': each channel-frame normalised by its own power after create_field (its GSTATE.POWER)
+        self.rx_gain = torch.sqrt(self.power_mw / self.tx_power).reshape(-1, 1, 1) if self.random else None
         if launch_scale is not None:
             ls = np.repeat(np.asarray(launch_scale, dtype=float).reshape(-1), nch)
             k = torch.as_tensor(np.sqrt(ls), device=self.dev).reshape(-1, 1)
@@ -445,14 +462,9 @@ class HotPath:
         self.pat_frames = torch.empty((ncf, 4, cfg.nsymb), dtype=torch.uint8, device=self.dev)
         self.dpat_frames = torch.empty_like(self.pat_frames)
         self.tx_power = torch.empty(ncf, dtype=torch.float64, device=self.dev)
-        kt = None
-        if data_keys is not None:
-            keys = np.asarray(list(data_keys), dtype=np.int64)
-            if keys.size != nframes:
-                raise ValueError("data_keys must hold one key per frame (%d), not %d" % (nframes, keys.size))
-            kt = torch.as_tensor(keys, device=self.dev)
+        kt = self._keys_dev(frame_keys(data_keys, nframes, "data_keys"))
         self.lib.call("plx_tx_qpsk_dev", ux.data_ptr(), uy.data_ptr(), cfg.nsymb, cfg.nt, nch, nframes,
-                      self.tx_drive.ctypes.data, float(cfg.pavg_mw), 20260101, kt.data_ptr() if kt is not None else None,
+                      self.tx_drive.ctypes.data, float(cfg.pavg_mw), MASTER_SEED, kt.data_ptr() if kt is not None else None,
                       self.pat_frames.data_ptr(), self.dpat_frames.data_ptr(), self.tx_power.data_ptr(), self.stream())
         self._batch += [self.pat_frames, self.dpat_frames, self.tx_power]
         if self.txfilt:        # band-limit every channel-frame and bring it back to pavg_mw by its own mean power
@@ -462,6 +474,10 @@ class HotPath:
             self._batch.append(self.tx_gain)
         return ux, uy
 
+    def _keys_dev(self, keys):
+        """frame_keys' array on the device (None for None)"""
+        return None if keys is None else self.torch.as_tensor(keys, device=self.dev)
+
     def batch_tensors(self):
         """the tensors make_batch made for the current batch beside ux, uy (patterns, power, receiver gain)"""
         return list(self._batch)
@@ -469,7 +485,7 @@ class HotPath:
     def tx_bits_host(self, keys):
         """[len(keys), nch, nsymb, 4] uint8: the data tx_data='random' transmits in the realisations `keys` (the host mirror
         synth.random_qpsk_bits; columns X first, X second, Y first, Y second)"""
-        return np.stack([np.stack([synth.random_qpsk_bits(self.cfg.nsymb, 20260101, int(k), c) for c in range(self.nch)])
+        return np.stack([np.stack([synth.random_qpsk_bits(self.cfg.nsymb, MASTER_SEED, int(k), c) for c in range(self.nch)])
                          for k in keys])
 
     def set_random_pmd(self, seeds):
@@ -481,7 +497,7 @@ class HotPath:
         plate = np.arange(np_, dtype=np.uint64).reshape(1, -1, 1)
         stream = np.arange(3, dtype=np.uint64).reshape(1, 1, 3)
         with np.errstate(over="ignore"):       # uint64 arithmetic wraps by design
-            keys = (np.uint64(20260101) * np.uint64(0x9E3779B97F4A7C15) + r) * np.uint64(0xD1342543DE82EF95) \
+            keys = (np.uint64(MASTER_SEED) * np.uint64(0x9E3779B97F4A7C15) + r) * np.uint64(0xD1342543DE82EF95) \
                 + plate * np.uint64(3) + stream
         u = _u01(keys)
         db0 = np.ascontiguousarray(u[:, :, 0] * 2 * math.pi - math.pi)
@@ -509,8 +525,9 @@ class HotPath:
         F = ux.shape[0]
         self._rows = self._steps = 0
         cfg = self.cfg
+        keys, kt = frame_keys(span_keys, F, "span_keys"), None
         if tx_phase is not None or cfg.tx_linewidth > 0:      # lasersource.m:182-192: one laser feeds X and Y
-            self._phase(ux.data_ptr(), uy.data_ptr(), 1, cfg.nfft, 1.0, F, span_keys, _abi.PLX_PHASE_TX, cfg.tx_linewidth,
+            self._phase(ux.data_ptr(), uy.data_ptr(), 1, cfg.nfft, 1.0, F, keys, _abi.PLX_PHASE_TX, cfg.tx_linewidth,
                         tx_phase)
         px, py = ux.data_ptr(), uy.data_ptr()
         if self.unique:
@@ -528,15 +545,13 @@ class HotPath:
                 gain = math.exp(self.alphalin * cfg.length)
                 sig = None
                 if cfg.span_nf_db is not None:
-                    from .ampliflat import ase_sigma
                     sig = np.ascontiguousarray(ase_sigma(cfg.span_nf_db, gain, self.nfc), dtype=float)
-                kt = None
-                if span_keys is not None:
-                    kt = self.torch.as_tensor(np.asarray(list(span_keys), dtype=np.int64), device=self.dev)
+                if kt is None:       # uploaded once per call: every amplifier reads the same keys
+                    kt = self._keys_dev(keys)
                 inj = inject_noise[namp] if inject_noise is not None else None
                 self.lib.call("plx_ampliflat_dev", px, py, cfg.nfft, self.nfc, F, gain,
                               sig.ctypes.data if sig is not None else None, inj.data_ptr() if inj is not None else None,
-                              (20260101 + 7919 * span) & (2 ** 64 - 1),
+                              (MASTER_SEED + 7919 * span) & (2 ** 64 - 1),
                               kt.data_ptr() if kt is not None else None, 1, 1, self.stream())
                 namp += 1
         if self.unique:
@@ -557,10 +572,8 @@ class HotPath:
         if work is None:
             work = self._phase_work[tag] = torch.empty(need, dtype=torch.float64, device=self.dev)
         sig = np.full(nch, math.sqrt(2 * math.pi * float(linewidth) / self.cfg.nt))
-        kt = None
-        if keys is not None:
-            kt = torch.as_tensor(np.asarray(list(keys), dtype=np.int64), device=self.dev)
-        self.lib.call("plx_phase_noise_dev", pu, pv, stride, pitch, sign, n, nch, F, sig.ctypes.data, 20260101,
+        kt = self._keys_dev(frame_keys(keys, F, "keys"))
+        self.lib.call("plx_phase_noise_dev", pu, pv, stride, pitch, sign, n, nch, F, sig.ctypes.data, MASTER_SEED,
                       kt.data_ptr() if kt is not None else None, tag, None, phi_out, work.data_ptr(), self.stream())
 
     def _phase_shape(self, phi, F):
@@ -591,9 +604,7 @@ class HotPath:
         the latency-bound CMA recurrence overlaps the HBM-bound fibre sweeps of the NEXT batch.
         lo_phase: optional [F, nch, n] float64 device tensor, the LO phase of each channel's receiver used INSTEAD of the
         cfg.lo_linewidth generator (keyed by noise_keys, or the frame index)."""
-        if side_stream is not None and not self.overlap_ok():
-            side_stream = None
-        if side_stream is not None:
+        if side_stream is not None and self.overlap_ok():
             torch = self.torch
             ready = torch.cuda.Event()
             ready.record(torch.cuda.current_stream())
@@ -601,27 +612,43 @@ class HotPath:
             with torch.cuda.stream(side_stream):
                 return self.receive(ux, uy, noise_sigma, noise_seed, None, noise_keys, lo_phase)
         F = ux.shape[0] * self.nch             # channel-frames: every channel of a 'sepfields' frame has its own receiver
-        cfg = self.cfg
-        half = cfg.nt // 2
-        st = self.stream()
-        rx = self.rx[:F]
+        cfg, st, rx = self.cfg, self.stream(), self.rx[:F]
         if self.nch > 1:
             ux, uy = ux.view(F, cfg.nfft), uy.view(F, cfg.nfft)
         Ff = F // self.nch                     # frames (the phase tensors are [Ff, nch, nfft])
+        keys = frame_keys(noise_keys, Ff, "noise_keys")
+        self._front_end(ux, uy, rx, F, Ff, keys, lo_phase)
+        if self.rx_gain is not None and self.front is None:   # launch-power ladder: each frame normalised by its own power
+            rx.mul_(self.rx_gain[:F])
+        if noise_sigma:
+            self._rx_noise(rx, F, Ff, noise_sigma, noise_seed, keys)
+        if self.dbp is not None:
+            sc = self._dbp_sc[:F]
+            if self.rx_gain is not None:     # launch-power ladder: rx carries each frame's own gain
+                sc = (sc / self.rx_gain[:F].reshape(-1)).contiguous()
+                self._dbp_sc_keep = sc       # alive until the kernel has run
+            self.dbp.apply(rx, self.eq, sc, st)
+        else:
+            self.lib.call("plx_cde_apply_dev", self.cde, rx.data_ptr(), self.eq.data_ptr(), self.Lrx, 2 * F, st)
+        self.lib.call("plx_dsp_run_dev", self.dsp, self.eq.data_ptr(), self.sym.data_ptr(), F, st)
+        return self._decide_count(F)
+
+    def _front_end(self, ux, uy, rx, F, Ff, keys, lo_phase):
+        """rx [F, 2, Lrx] <- the 2-sps samples of the channel-frames ux, uy [F, nfft]: cohmix, or (channel filter +) pick + LO"""
+        cfg, st, half = self.cfg, self.stream(), self.cfg.nt // 2
         lo = lo_phase is not None or cfg.lo_linewidth > 0
         if self.front is not None:             # receiver_cohmix + ADC + decimate; ux, uy are consumed
             if self.rx_gain is not None:       # launch-power ladder: each frame normalised by its own power
                 ux.mul_(self.rx_gain[:F, :, 0])
                 uy.mul_(self.rx_gain[:F, :, 0])
-            lop = None
+            lop = lo_phase
             if lo_phase is not None:
                 self._phase_shape(lo_phase, Ff)
-                lop = lo_phase
             elif lo:                           # Elo[f] = Elo exp(i phi_b[f]) (receiver_cohmix.m:223): phi_b of every channel-frame
                 if self._lo_buf is None:
                     self._lo_buf = self.torch.empty((self.CF, cfg.nfft), dtype=self.torch.float64, device=self.dev)
                 lop = self._lo_buf
-                self._phase(None, None, 1, cfg.nfft, 1.0, Ff, noise_keys, _abi.PLX_PHASE_LO, cfg.lo_linewidth, None,
+                self._phase(None, None, 1, cfg.nfft, 1.0, Ff, keys, _abi.PLX_PHASE_LO, cfg.lo_linewidth, None,
                             lop.data_ptr())
             self.front.run(ux, uy, self.front_shifts, out=rx, lo_phase=lop)
         else:
@@ -632,75 +659,54 @@ class HotPath:
                 self.lib.call("plx_pick_dev", src.data_ptr(), rx.data_ptr() + pol * self.Lrx * 16, cfg.nfft, self.Lrx, 0,
                               half, self.rx_scale, F, 2 * self.Lrx, st)
             if lo:                             # the LO at the pick instants: rx[f][pol][i] *= exp(-i phi_b[f][i half])
-                self._phase(rx.data_ptr(), rx.data_ptr() + self.Lrx * 16, half, 2 * self.Lrx, -1.0, Ff, noise_keys,
+                self._phase(rx.data_ptr(), rx.data_ptr() + self.Lrx * 16, half, 2 * self.Lrx, -1.0, Ff, keys,
                             _abi.PLX_PHASE_LO, cfg.lo_linewidth, lo_phase)
-        if self.rx_gain is not None and self.front is None:   # launch-power ladder: each frame normalised by its own power
-            rx.mul_(self.rx_gain[:F])
-        if noise_sigma:
-            kt, nf, ncol = None, F, 1
-            if noise_keys is not None:
-                keys = np.asarray(list(noise_keys), dtype=np.int64)
-                if keys.size != Ff:
-                    raise ValueError("noise_keys must hold one key per frame (%d), not %d" % (Ff, keys.size))
-                kt = self.torch.as_tensor(keys, device=self.dev)
-                # one key per FRAME (realisation): the nch channel-frames of a frame are the columns of one ampliflat frame,
-                # so each draws its own stream (the column is a word of the Philox counter) under its realisation's key
-                nf, ncol = Ff, self.nch
-            sig = np.full(ncol, float(noise_sigma))
-            # one channel-frame of rx = [X | Y] contiguous: a single-"polarisation" ampliflat column with unit gain
-            self.lib.call("plx_ampliflat_dev", rx.data_ptr(), None, 2 * self.Lrx, ncol, nf, 1.0, sig.ctypes.data, None,
-                          int(noise_seed or 0) & (2 ** 64 - 1), kt.data_ptr() if kt is not None else None, 1, 0, st)
-        if self.dbp is not None:
-            sc = self._dbp_sc[:F]
-            if self.rx_gain is not None:     # launch-power ladder: rx carries each frame's own gain
-                sc = (sc / self.rx_gain[:F].reshape(-1)).contiguous()
-                self._dbp_sc_keep = sc       # alive until the kernel has run
-            self.dbp.apply(rx, self.eq, sc, st)
+
+    def _rx_noise(self, rx, F, Ff, noise_sigma, noise_seed, keys):
+        """noise of sigma per quadrature on the 2-sps samples rx [F, 2, Lrx], keyed by (noise_seed, keys[frame] or channel-frame)"""
+        kt, nf, ncol = self._keys_dev(keys), F, 1
+        if kt is not None:
+            # one key per FRAME (realisation): the nch channel-frames of a frame are the columns of one ampliflat frame,
+            # so each draws its own stream (the column is a word of the Philox counter) under its realisation's key
+            nf, ncol = Ff, self.nch
+        sig = np.full(ncol, float(noise_sigma))
+        # one channel-frame of rx = [X | Y] contiguous: a single-"polarisation" ampliflat column with unit gain
+        self.lib.call("plx_ampliflat_dev", rx.data_ptr(), None, 2 * self.Lrx, ncol, nf, 1.0, sig.ctypes.data, None,
+                      int(noise_seed or 0) & (2 ** 64 - 1), kt.data_ptr() if kt is not None else None, 1, 0, self.stream())
+
+    def _decide_count(self, F, swap=False):
+        """the view self.err[:F] ([F, 2]) of the symbols now in self.sym against the transmitted bits (tributaries exchanged if swap)"""
+        cfg, st = self.cfg, self.stream()
+        pat = self.pat_frames[:F] if self.per_frame else self.pat
+        if swap:
+            pat = self.torch.cat([pat[..., 2:, :], pat[..., :2, :]], -2).contiguous()
+        self._pat_keep = pat              # alive until the kernel has run
+        if self.per_frame:
+            self.lib.call("plx_decide_count_frames_dev", self.sym.data_ptr(), cfg.nsymb, 2, F, pat.data_ptr(), 4 * cfg.nsymb,
+                          None, self.err.data_ptr(), st)
         else:
-            self.lib.call("plx_cde_apply_dev", self.cde, rx.data_ptr(), self.eq.data_ptr(), self.Lrx, 2 * F, st)
-        self.lib.call("plx_dsp_run_dev", self.dsp, self.eq.data_ptr(), self.sym.data_ptr(), F, st)
-        if self.per_frame:    # frames carry different sequences: each compares with its own transmitted bits
-            self.lib.call("plx_decide_count_frames_dev", self.sym.data_ptr(), cfg.nsymb, 2, F, self.pat_frames.data_ptr(),
-                          4 * cfg.nsymb, None, self.err.data_ptr(), st)
-        else:
-            self.lib.call("plx_decide_count_dev", self.sym.data_ptr(), cfg.nsymb, 2, F, self.pat.data_ptr(), None,
+            self.lib.call("plx_decide_count_dev", self.sym.data_ptr(), cfg.nsymb, 2, F, pat.data_ptr(), None,
                           self.err.data_ptr(), st)
         return self.err[:F]
 
-    def _count_errors(self, F, swap):
-        """err [F, 2] of the symbols now in self.sym against the transmitted bits (tributaries exchanged if swap)."""
-        torch = self.torch
-        if self.per_frame:
-            pat = self.pat_frames[:F]
-            if swap:
-                pat = torch.cat([pat[:, 2:], pat[:, :2]], 1).contiguous()
-            self._pat_keep = pat          # alive until the kernel has run
-            self.lib.call("plx_decide_count_frames_dev", self.sym.data_ptr(), self.cfg.nsymb, 2, F, pat.data_ptr(),
-                          4 * self.cfg.nsymb, None, self.err.data_ptr(), self.stream())
-        else:
-            pat = torch.cat([self.pat[2:], self.pat[:2]]).contiguous() if swap else self.pat
-            self._pat_keep = pat
-            self.lib.call("plx_decide_count_dev", self.sym.data_ptr(), self.cfg.nsymb, 2, F, pat.data_ptr(), None,
-                          self.err.data_ptr(), self.stream())
-        return self.err[:F].clone()
+    def _min_over_rotations(self, F, swap, base):
+        """err [F, 2]: minimum of the counts over the four pi/2 rotations of base, a clone of self.sym[:F] (the caller restores it)"""
+        best = None
+        for k in range(4):
+            self.sym[:F] = base * (1j ** k)
+            e = self._decide_count(F, swap).clone()
+            best = e if best is None else self.torch.minimum(best, e)
+        return best
 
     def errors_resolved(self, F):
         """Per-frame bit errors after resolving what a blind receiver cannot know: the pi/2 phase
         ambiguity of the Viterbi&Viterbi estimate (per polarisation) and which CMA output carries which
         transmitted tributary (the pol-swap check of ex20_coherent_polmux.m:160-173).  Eight calls of
         the device decision/count kernel; returns an int64 tensor [F]."""
-        torch = self.torch
         base = self.sym[:F].clone()
-        best = []
-        for swap in (False, True):
-            b = None
-            for k in range(4):
-                self.sym[:F] = base * (1j ** k)
-                e = self._count_errors(F, swap)
-                b = e if b is None else torch.minimum(b, e)
-            best.append(b.sum(1))
+        best = [self._min_over_rotations(F, swap, base).sum(1) for swap in (False, True)]
         self.sym[:F] = base
-        return torch.minimum(best[0], best[1])
+        return self.torch.minimum(best[0], best[1])
 
     def evm(self, F):
         """per-frame error-vector magnitude (mean |s - s_hat|^2) of the symbols now in self.sym: float64 tensor [F]"""
@@ -711,13 +717,8 @@ class HotPath:
     def errors_min_over_rotations(self, F):
         """Resolve the pi/2 ambiguity of the blind phase estimate per polarisation (host-side
         convenience for BER sanity; the reference's scripts use differential decoding instead)."""
-        torch = self.torch
-        best = None
         base = self.sym[:F].clone()
-        for k in range(4):
-            self.sym[:F] = base * (1j ** k)
-            e = self._count_errors(F, False)
-            best = e if best is None else torch.minimum(best, e)
+        best = self._min_over_rotations(F, False, base)
         self.sym[:F] = base
         return best
 
@@ -766,8 +767,9 @@ class HotPath:
         GSTATE.NSYMB, GSTATE.NT, GSTATE.NCH = cfg.nsymb, cfg.nt, self.nch
         GSTATE.SYMBOLRATE = cfg.symbolrate
         GSTATE.FN = synth.fn_grid(cfg.nsymb, cfg.nt)
-        GSTATE.LAMBDA = cfg.lam + cfg.chspacing * (np.arange(self.nch) - (self.nch - 1) / 2)
-        GSTATE.POWER = np.full(self.nch, self.power_mw)
+        GSTATE.LAMBDA = cfg.lam + cfg.chspacing * (np.arange(self.nch) - (self.nch - 1) / 2)      # lasersource.m: equally spaced comb
+        if self.power_mw is not None:    # (known once the transmitter is built)
+            GSTATE.POWER = np.full(self.nch, self.power_mw)
 
     def tx_columns(self):
         """Tx field of ONE frame as MATLAB holds it: (ux, uy), each [nfft x nch] (column c = variant c % variants)"""
@@ -776,8 +778,7 @@ class HotPath:
 
     def row_kernel(self):
         """name of the kernel that serves the step's row pass (for reports)"""
-        info = (C.c_int32 * 8)()
-        self.lib.call("plx_ssfm_info", self.ssfm, info)
+        info = self.info()
         if info[6] == 64:
             return "k_row256r" if info[2] == 8 else "k_rowsm"    # (rows of 32 / 64 / 128 points)
         if info[7] == 2:
@@ -791,8 +792,7 @@ class HotPath:
         the tiles of a frame co-resident; when ONE frame takes more than half of the grid (2^19- and 2^20-sample frames)
         a long-running receiver kernel that holds registers on every CU keeps the frame's second half from being placed
         until it ends: the two serialise (or the barrier times out).  Such plans run the receiver on the fibre's stream."""
-        info = (C.c_int32 * 8)()
-        self.lib.call("plx_ssfm_info", self.ssfm, info)
+        info = self.info()
         return (not info[0]) or 2 * info[4] <= info[3]
 
     def ssfm_stats(self):
@@ -800,7 +800,20 @@ class HotPath:
         return self._rows, self._steps
 
 
-class McCampaign:
+def _concat(parts, dtype):
+    """the parts of a campaign's result side by side (an empty result for no part)"""
+    return np.concatenate(parts) if parts else np.zeros(0, dtype)
+
+
+class _Simulate:
+    def simulate(self, indices, keep=None):
+        """Error counts (pol swap and pi/2 ambiguities resolved, ex20_coherent_polmux.m:160-173) of the realisations
+        `indices`.  keep(i0, idx, ux, uy): optional callback after the fibre + amplifier of each batch (tests read the
+        field back there)."""
+        return self.collect(self.launch(indices, keep))
+
+
+class McCampaign(_Simulate):
     """Monte-Carlo BER over random PMD + ASE realisations (the ex20-style loop around ber_estimate,
     with ex24's random-birefringence fibre): realisation r gets its own birefringence draw and its own
     noise, both keyed by r alone, so any sharding of the indices over GPUs gives the same counts.
@@ -848,7 +861,7 @@ class McCampaign:
             # it by itself, and the EVM / error kernels must follow the DSP in stream order)
             rxs = self._rx_stream if hp.overlap_ok() else torch.cuda.current_stream()
             side = rxs if rxs is self._rx_stream else None
-            hp.receive(ux, uy, self.sigma, 20260101, side, idx)   # receiver noise keyed by realisation index
+            hp.receive(ux, uy, self.sigma, MASTER_SEED, side, idx)   # receiver noise keyed by realisation index
             with torch.cuda.stream(rxs):
                 ncf = n * hp.nch if hp.unique else n    # a 'unique' comb: a count per channel-frame, [n nch], channels innermost
                 v = hp.evm(ncf)            # a continuous per-realisation sample (mc_estimate) beside the error count
@@ -870,22 +883,13 @@ class McCampaign:
             done.synchronize()             # the counts were formed on the receiver's stream
             res.append(e.cpu().numpy())
             smp.append(v.cpu().numpy())
-        counts = np.concatenate(res) if res else np.zeros(0, np.int64)
-        if with_samples:
-            return counts, (np.concatenate(smp) if smp else np.zeros(0))
-        return counts
-
-    def simulate(self, indices, keep=None):
-        """Error counts (pol swap and pi/2 ambiguities resolved, ex20_coherent_polmux.m:160-173) of the realisations
-        `indices`.  keep(i0, idx, ux, uy): optional callback after the fibre + amplifier of each batch (tests read the
-        field back there)."""
-        return self.collect(self.launch(indices, keep))
+        return (_concat(res, np.int64), _concat(smp, np.float64)) if with_samples else _concat(res, np.int64)
 
     def close(self):
         self.hp.close()
 
 
-class McRankShare:
+class McRankShare(_Simulate):
     """The share ONE rank of `world` has in a campaign, run on its own: local index i stands for realisation rank + world * i
     (realisation r on GPU r mod world).  launch / collect / simulate of the wrapped campaign or pool."""
 
@@ -901,11 +905,8 @@ class McRankShare:
     def collect(self, handle, with_samples=False):
         return self.camp.collect(handle, with_samples)
 
-    def simulate(self, indices, keep=None):
-        return self.collect(self.launch(indices, keep))
 
-
-class McCampaignPool:
+class McCampaignPool(_Simulate):
     """`n` McCampaign instances taking the rounds of a campaign in turn, each with its own plans, receiver buffers and
     receiver stream: the receivers of up to n rounds are in flight at once (ShardedBer.run(depth=n - 1)).  A noise-loaded
     realisation's CMA runs all of its 299 passes -- ~58 ms of a serial recurrence whatever the batch size -- while its
@@ -938,16 +939,11 @@ class McCampaignPool:
 
     def collect(self, handle, with_samples=False):
         if self.split:
-            parts = [self.camps[i].collect(h, with_samples) for i, h in handle]
-            if with_samples:
-                return (np.concatenate([p[0] for p in parts]) if parts else np.zeros(0, np.int64),
-                        np.concatenate([p[1] for p in parts]) if parts else np.zeros(0))
-            return np.concatenate(parts) if parts else np.zeros(0, np.int64)
+            parts = [self.camps[i].collect(h, True) for i, h in handle]
+            counts, smp = _concat([p[0] for p in parts], np.int64), _concat([p[1] for p in parts], np.float64)
+            return (counts, smp) if with_samples else counts
         i, h = handle
         return self.camps[i].collect(h, with_samples)
-
-    def simulate(self, indices, keep=None):
-        return self.collect(self.launch(indices, keep))
 
     def close(self):
         for c in self.camps:

@@ -46,7 +46,7 @@ def measure(torch, pipeline, name, F, reps, **kw):
         ux, uy = hp.make_batch(F)                      # (its tensors are this batch's: the calls below write into them again)
         px, py = ux.data_ptr(), uy.data_ptr()
         tx = timed(torch, lambda: lib.call("plx_tx_qpsk_dev", px, py, cfg.nsymb, cfg.nt, nch, F, hp.tx_drive.ctypes.data,
-                                           float(cfg.pavg_mw), 20260101, None, hp.pat_frames.data_ptr(), hp.dpat_frames.data_ptr(),
+                                           float(cfg.pavg_mw), pipeline.MASTER_SEED, None, hp.pat_frames.data_ptr(), hp.dpat_frames.data_ptr(),
                                            hp.tx_power.data_ptr(), st), reps)
         bl = timed(torch, lambda: lib.call("plx_tx_bandlimit_dev", hp.txfilt, px, py, npairs, float(cfg.pavg_mw),
                                            hp.tx_gain.data_ptr(), hp._txfilt_work.data_ptr(), st), reps)
