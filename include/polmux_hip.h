@@ -233,6 +233,12 @@ int plx_scalar_ssfm_adaptive(double *ur, double *ui, const plx_ssfm_desc *desc, 
  * the fftshift-ordered grid (CDE_OFDE.m:30-38), both interleaved complex128.       */
 typedef struct plx_cde plx_cde;
 int plx_cde_create(plx_cde **plan, int64_t fft_len, int64_t L, const double *H_interleaved);
+/* the same with one table per WDM channel: H [nch][fft_len], each on the fftshift-ordered grid; row r of an
+ * apply call uses table (r / rows_per_channel) % nch (rows_per_channel = 2: X and Y of a channel-frame, channels innermost).
+ * The checks and messages of plx_cde_create, plus 1 <= nch <= 64 and rows_per_channel >= 1 (PLX_ERR_ARG).  A workgroup
+ * stages its row's table in LDS when fft_len <= 1024 and reads it from global memory above that, as for one table.  */
+int plx_cde_create_wdm(plx_cde **plan, int64_t fft_len, int64_t L, const double *H_interleaved, int32_t nch,
+                       int32_t rows_per_channel);
 int plx_cde_destroy(plx_cde *plan);
 int plx_cde_apply_dev(plx_cde *plan, const double *d_x, double *d_y, int64_t nx, int nsig, void *stream);
 /* gateway: the whole CDE_OFDE(inX, inY, fs, lambdaRef, span, D, S, fftLength, L) call,
@@ -465,6 +471,16 @@ int plx_wdm_mux_dev(const double *d_sx, const double *d_sy, double *d_ux, double
                     int nframes, const int64_t *shift, void *stream);
 int plx_wdm_select_dev(const double *d_ux, const double *d_uy, double *d_rx, double *d_ry, int64_t nfft, int32_t nch,
                        int nframes, const int64_t *shift, const int64_t *delay, void *stream);
+/* The 2-sps pick of 'sepfields' channel-frames, every channel at its own walk-off delay.  For channel-frame
+ * cf = f nch + c, polarisation p and i < n_out:
+ *   rx[cf][p][i] = scale * u_p[cf][(i stride + delay[c]) mod nfft]
+ * d_ux, d_uy: [nframes nch][nfft] complex128; d_rx: [nframes nch][2][n_out].  Both polarisations and all channel-frames in
+ * ONE launch; delay is a HOST array [nch], copied into the kernel's argument block: no allocation, no synchronisation.
+ * With every delay 0 the result equals two plx_pick_dev calls (offset 0, out_pitch 2 n_out) bit for bit.
+ * PLX_ERR_ARG: a null pointer; nfft outside [1, 2^30]; nch outside [1, 64]; nframes nch outside [1, 65535]; n_out or
+ * stride < 1 or n_out stride > nfft; |delay[c]| >= nfft.                                                              */
+int plx_pick_wdm_dev(const double *d_ux, const double *d_uy, double *d_rx, int64_t nfft, int64_t n_out, int64_t stride,
+                     double scale, int32_t nch, int nframes, const int64_t *delay, void *stream);
 
 /* ------------------------------------------------------------ coherent front end --- */
 /* The step between fiber() and CDE_OFDE(): receiver_cohmix.m:165-307 (optical filter x post-compensation,

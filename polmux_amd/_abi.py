@@ -109,6 +109,7 @@ SIGNATURES = {
     "plx_scalar_ssfm_adaptive": [_vp, _vp, C.POINTER(SsfmDesc), C.c_int, _dbl, _dbl, C.POINTER(_dbl), C.POINTER(_i32),
                                  C.POINTER(_i32)],
     "plx_cde_create": [C.POINTER(_vp), _i64, _i64, _vp],
+    "plx_cde_create_wdm": [C.POINTER(_vp), _i64, _i64, _vp, _i32, _i32],
     "plx_cde_destroy": [_vp],
     "plx_cde_apply_dev": [_vp, _vp, _vp, _i64, C.c_int, _vp],
     "plx_cde_ofde": [_vp, _vp, _vp, _vp, _i64, _dbl, _dbl, _dbl, _dbl, _dbl, _i64, _i64, _vp, _vp, _vp, _vp],
@@ -137,6 +138,7 @@ SIGNATURES = {
     "plx_tx_qpsk_dev": [_vp, _vp, _i64, _i32, _i32, C.c_int, _vp, _dbl, C.c_uint64, _vp, _vp, _vp, _vp, _vp],
     "plx_wdm_mux_dev": [_vp, _vp, _vp, _vp, _i64, _i32, C.c_int, _vp, _vp],
     "plx_wdm_select_dev": [_vp, _vp, _vp, _vp, _i64, _i32, C.c_int, _vp, _vp, _vp],
+    "plx_pick_wdm_dev": [_vp, _vp, _vp, _i64, _i64, _i64, _dbl, _i32, C.c_int, _vp, _vp],
     "plx_front_create": [C.POINTER(_vp), C.POINTER(FrontDesc)],
     "plx_front_destroy": [_vp],
     "plx_front_out_len": [_vp],

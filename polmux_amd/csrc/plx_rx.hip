@@ -34,10 +34,11 @@ namespace {
 struct CdeArgs {
     const cplx *x;
     cplx *y;
-    const cplx *Hp;  // [N] H at bit-reversed bins, fftshift undone, times 1/N
+    const cplx *Hp;  // [ntab][N] H at bit-reversed bins, fftshift undone, times 1/N
     const cplx *tw;  // half table W_N^k
     int64_t nx;
     int logN, L, B2, G, logG, nblocks, h_in_lds;
+    int ntab, rpt;   // tables of the plan; row r uses table (r / rpt) % ntab (plx_cde_create: 1, 1)
 };
 
 // OverlapBothTrans, CDE_OFDE.m:88-124
@@ -50,10 +51,12 @@ __global__ __launch_bounds__(256) void k_cde(CdeArgs a)
     cplx *tw = s + (size_t)a.G * N;   // [N/2]
     cplx *Hl = tw + (N >> 1);         // [N] when staged
     lds_load_twiddles(tw, a.tw, N >> 1, tid, nthr);
-    if (a.h_in_lds)
-        for (int k = tid; k < N; k += nthr) Hl[k] = a.Hp[k];
-    const cplx *H = a.h_in_lds ? Hl : a.Hp;
     const size_t sig = blockIdx.y;
+    // a workgroup serves one row: its channel's table (wave-uniform; a one-table plan never divides)
+    const cplx *Hg = a.ntab > 1 ? a.Hp + (size_t)(((unsigned)blockIdx.y / (unsigned)a.rpt) % (unsigned)a.ntab) * N : a.Hp;
+    if (a.h_in_lds)
+        for (int k = tid; k < N; k += nthr) Hl[k] = Hg[k];
+    const cplx *H = a.h_in_lds ? Hl : Hg;
     const cplx *x = a.x + sig * (size_t)a.nx;
     cplx *y = a.y + sig * (size_t)a.nx;
     const int b0 = blockIdx.x * a.G;
@@ -875,6 +878,7 @@ template <class K> hipError_t allow_lds(K, size_t) { return hipSuccess; }
 struct plx_cde {
     int64_t N, L;
     int logN, G, h_in_lds;
+    int ntab = 1, rpt = 1;   // tables, rows per table (plx_cde_create_wdm)
     cplx *d_H = nullptr, *d_tw = nullptr;
     size_t lds = 0;
 };
@@ -883,30 +887,36 @@ static const char *kCdeMsg[] = {"", "Error: x must be one dimensional complex ve
                                 "Error: L must be > 0", "Error: L must be shorter than filter length",
                                 "Error: Signal must be longer or equal filter"};
 
-extern "C" int plx_cde_create(plx_cde **out, int64_t fft_len, int64_t L, const double *H)
+// the checks, the table layout and the uploads of both create calls: H holds ntab tables of fft_len bins, one behind the other
+static int cde_create(const std::string &who, plx_cde **out, int64_t fft_len, int64_t L, const double *H, int32_t ntab, int32_t rpt)
 {
-    if (!out || !H) PLX_FAIL(PLX_ERR_ARG, "plx_cde_create: null argument");
+    if (!out || !H) PLX_FAIL(PLX_ERR_ARG, who + ": null argument");
     *out = nullptr;
     if (fft_len % 2 != 0) PLX_FAIL(PLX_ERR_ARG, kCdeMsg[2]);     // CDE_OFDE.m:73-74
     if (L <= 0) PLX_FAIL(PLX_ERR_ARG, kCdeMsg[3]);               // :77-78
     if (L > fft_len) PLX_FAIL(PLX_ERR_ARG, kCdeMsg[4]);          // :79-80
     const int logN = ilog2i(fft_len);
     if (((int64_t)1 << logN) != fft_len || fft_len < 4 || fft_len > 4096)
-        PLX_FAIL(PLX_ERR_UNSUPPORTED, "plx_cde_create: FFT length must be a power of two in [4, 4096]");
-    if ((fft_len - L) % 2 != 0) PLX_FAIL(PLX_ERR_UNSUPPORTED, "plx_cde_create: overlap N-L must be even");
+        PLX_FAIL(PLX_ERR_UNSUPPORTED, who + ": FFT length must be a power of two in [4, 4096]");
+    if ((fft_len - L) % 2 != 0) PLX_FAIL(PLX_ERR_UNSUPPORTED, who + ": overlap N-L must be even");
+    if (ntab < 1 || ntab > 64) PLX_FAIL(PLX_ERR_ARG, who + ": nch must be in [1, 64]");
+    if (rpt < 1) PLX_FAIL(PLX_ERR_ARG, who + ": rows_per_channel must be >= 1");
     plx_cde *P = new plx_cde();
-    P->N = fft_len; P->L = L; P->logN = logN;
+    P->N = fft_len; P->L = L; P->logN = logN; P->ntab = ntab; P->rpt = rpt;
     int G = 1;
     while (G < 8 && (int64_t)G * 2 * fft_len <= 2048) G *= 2;
     P->G = G;
     P->h_in_lds = fft_len <= 1024 ? 1 : 0;
     // H is given on the fftshift-ordered grid: unshifted bin k takes H[(k+N/2) mod N]
     // (CDE_OFDE.m:108-112); LDS position i holds bin bitrev(i); fold in ifft's 1/N.
-    std::vector<cplx> Hp((size_t)fft_len), tw((size_t)(fft_len / 2));
-    for (int64_t i = 0; i < fft_len; i++) {
-        const int64_t k = (int64_t)plx_bitrev((unsigned)i, logN);
-        const int64_t src = (k + fft_len / 2) % fft_len;
-        Hp[i] = make_double2(H[2 * src] / (double)fft_len, H[2 * src + 1] / (double)fft_len);
+    std::vector<cplx> Hp((size_t)ntab * (size_t)fft_len), tw((size_t)(fft_len / 2));
+    for (int64_t t = 0; t < ntab; t++) {
+        const double *Ht = H + 2 * t * fft_len;
+        for (int64_t i = 0; i < fft_len; i++) {
+            const int64_t k = (int64_t)plx_bitrev((unsigned)i, logN);
+            const int64_t src = (k + fft_len / 2) % fft_len;
+            Hp[(size_t)(t * fft_len + i)] = make_double2(Ht[2 * src] / (double)fft_len, Ht[2 * src + 1] / (double)fft_len);
+        }
     }
     for (int64_t k = 0; k < fft_len / 2; k++) {
         long double ang = -2.0L * 3.14159265358979323846264338327950288L * (long double)k / (long double)fft_len;
@@ -917,12 +927,22 @@ extern "C" int plx_cde_create(plx_cde **out, int64_t fft_len, int64_t L, const d
         hipMemcpy(P->d_H, Hp.data(), Hp.size() * sizeof(cplx), hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(P->d_tw, tw.data(), tw.size() * sizeof(cplx), hipMemcpyHostToDevice) != hipSuccess) {
         plx_cde_destroy(P);
-        PLX_FAIL(PLX_ERR_HIP, "plx_cde_create: device allocation/upload failed");
+        PLX_FAIL(PLX_ERR_HIP, who + ": device allocation/upload failed");
     }
     P->lds = ((size_t)G * fft_len + fft_len / 2 + (P->h_in_lds ? fft_len : 0)) * sizeof(cplx);
-    if (allow_lds(k_cde, P->lds) != hipSuccess) { plx_cde_destroy(P); PLX_FAIL(PLX_ERR_HIP, "plx_cde_create: cannot reserve LDS"); }
+    if (allow_lds(k_cde, P->lds) != hipSuccess) { plx_cde_destroy(P); PLX_FAIL(PLX_ERR_HIP, who + ": cannot reserve LDS"); }
     *out = P;
     return PLX_OK;
+}
+
+extern "C" int plx_cde_create(plx_cde **out, int64_t fft_len, int64_t L, const double *H)
+{
+    return cde_create("plx_cde_create", out, fft_len, L, H, 1, 1);
+}
+
+extern "C" int plx_cde_create_wdm(plx_cde **out, int64_t fft_len, int64_t L, const double *H, int32_t nch, int32_t rows_per_channel)
+{
+    return cde_create("plx_cde_create_wdm", out, fft_len, L, H, nch, rows_per_channel);
 }
 
 extern "C" int plx_cde_destroy(plx_cde *P)
@@ -939,7 +959,7 @@ extern "C" int plx_cde_apply_dev(plx_cde *P, const double *d_x, double *d_y, int
     CdeArgs a;
     a.x = (const cplx *)d_x; a.y = (cplx *)d_y; a.Hp = P->d_H; a.tw = P->d_tw; a.nx = nx;
     a.logN = P->logN; a.L = (int)P->L; a.B2 = (int)((P->N - P->L) / 2); a.G = P->G; a.logG = ilog2i(P->G);
-    a.nblocks = (int)((nx + P->L - 1) / P->L); a.h_in_lds = P->h_in_lds;
+    a.nblocks = (int)((nx + P->L - 1) / P->L); a.h_in_lds = P->h_in_lds; a.ntab = P->ntab; a.rpt = P->rpt;
     const unsigned gx = (unsigned)((a.nblocks + a.G - 1) / a.G);
     PLX_LAUNCH(k_cde, dim3(gx, (unsigned)nsig), dim3(256), P->lds, stream, a);
     PLX_HIP(hipGetLastError());

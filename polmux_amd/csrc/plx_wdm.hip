@@ -5,6 +5,11 @@
 // Both are streaming kernels: one lane per sample (16-B loads and stores, consecutive lanes on consecutive samples), the
 // channels of a sample in the lane's loop.  The phase s_c n is reduced modulo N in integers (N is a power of two, so the
 // 32-bit product may wrap) and becomes an exact number of turns k / N for cexp_neg_turns: no error grows with n.
+//
+// The receiver of 'sepfields' frames with per-channel timing: the 2-sps pick of every channel-frame at its own
+// channel's walk-off delay,
+//   pick     rx[cf][p][i] = scale * u_p[cf][(i stride + delay[c]) mod N],  cf = f nch + c
+// one lane per output sample (one 16-B load, one 16-B store), both polarisations and all channel-frames in one launch.
 #include "../../include/polmux_hip.h"
 #include "plx_common.h"
 
@@ -101,6 +106,27 @@ __global__ __launch_bounds__(256) void k_wdm_select(WdmArgs a)
     }
 }
 
+struct PickWdmArgs {
+    const cplx *ux, *uy;         // [channel-frame][nfft]
+    cplx *rx;                    // [channel-frame][2][n_out]
+    unsigned nfft, n_out, stride;
+    int nch;
+    double scale;
+    unsigned delay[WDM_MAXCH];   // delay[c] mod nfft, in [0, nfft)
+};
+
+// grid (ceil(n_out / 256), 2, channel-frames): i stride < nfft and delay < nfft, so one subtraction wraps the source index
+__global__ __launch_bounds__(256) void k_pick_wdm(PickWdmArgs a)
+{
+    const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.n_out) return;
+    const unsigned p = blockIdx.y, cf = blockIdx.z;
+    unsigned m = i * a.stride + a.delay[cf % (unsigned)a.nch];
+    if (m >= a.nfft) m -= a.nfft;
+    const cplx *u = p ? a.uy : a.ux;
+    a.rx[((size_t)cf * 2 + p) * a.n_out + i] = cscale(u[(size_t)cf * a.nfft + m], a.scale);
+}
+
 // the checks both calls share; fills the argument block
 int wdm_args(const char *who, WdmArgs &a, const void *cx, const void *cy, const void *ux, const void *uy, int64_t nfft,
              int32_t nch, int nframes, const int64_t *shift, const int64_t *delay)
@@ -151,6 +177,29 @@ extern "C" int plx_wdm_select_dev(const double *d_ux, const double *d_uy, double
     const int rc = wdm_args("plx_wdm_select_dev", a, d_rx, d_ry, d_ux, d_uy, nfft, nch, nframes, shift, delay);
     if (rc) return rc;
     PLX_LAUNCH(k_wdm_select, dim3(wdm_grid(nfft), (unsigned)nframes), dim3(256), 0, stream, a);
+    PLX_HIP(hipGetLastError());
+    return PLX_OK;
+}
+
+extern "C" int plx_pick_wdm_dev(const double *d_ux, const double *d_uy, double *d_rx, int64_t nfft, int64_t n_out, int64_t stride,
+                                double scale, int32_t nch, int nframes, const int64_t *delay, void *stream)
+{
+    const std::string w("plx_pick_wdm_dev");
+    if (!d_ux || !d_uy || !d_rx || !delay) PLX_FAIL(PLX_ERR_ARG, w + ": null argument");
+    if (nfft < 1 || nfft > ((int64_t)1 << 30)) PLX_FAIL(PLX_ERR_ARG, w + ": nfft must be in [1, 2^30]");
+    if (nch < 1 || nch > WDM_MAXCH) PLX_FAIL(PLX_ERR_ARG, w + ": nch must be in [1, 64]");
+    if (nframes < 1 || (int64_t)nframes * nch > 65535) PLX_FAIL(PLX_ERR_ARG, w + ": nframes * nch must be in [1, 65535]");
+    if (n_out < 1 || stride < 1 || n_out > nfft || stride > nfft || n_out * stride > nfft)
+        PLX_FAIL(PLX_ERR_ARG, w + ": selection out of range (n_out * stride must not exceed nfft)");
+    PickWdmArgs a;
+    a.ux = (const cplx *)d_ux; a.uy = (const cplx *)d_uy; a.rx = (cplx *)d_rx;
+    a.nfft = (unsigned)nfft; a.n_out = (unsigned)n_out; a.stride = (unsigned)stride; a.nch = nch; a.scale = scale;
+    for (int c = 0; c < WDM_MAXCH; c++) a.delay[c] = 0;
+    for (int c = 0; c < nch; c++) {
+        if (delay[c] <= -nfft || delay[c] >= nfft) PLX_FAIL(PLX_ERR_ARG, w + ": |delay[c]| must be below nfft");
+        a.delay[c] = (unsigned)((delay[c] + nfft) % nfft);
+    }
+    PLX_LAUNCH(k_pick_wdm, dim3((unsigned)((n_out + 255) / 256), 2, (unsigned)(nframes * nch)), dim3(256), 0, stream, a);
     PLX_HIP(hipGetLastError());
     return PLX_OK;
 }

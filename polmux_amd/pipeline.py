@@ -55,7 +55,7 @@ class HotPathConfig:
                  adcbits=5, span_nf_db=None, rx_amp=False, variants=1, nch=1, chspacing=0.4, share_device=False,
                  equaliser="cde", dbp_steps=4, dbp_xi=1.0, tx_linewidth=0.0, lo_linewidth=0.0, decoding="rotation",
                  xpm_dualpol=None, wdm_field="sepfields", mux_filter=None, tx_data="debruijn",
-                 tx_filter=None):
+                 tx_filter=None, wdm_receiver=None):
         """frontend: 'pick' = 2-sps sampling supplied by the harness; 'cohmix' = the reference's own
         receiver_cohmix + ADC + decimate chain (RxPdmCohQpsk.m, Run_my_PDM_QPSK.m:52-73 defaults) on the device.
         nspans > 1: every span but the last is followed by an in-line flat amplifier restoring its loss
@@ -109,7 +109,17 @@ class HotPathConfig:
         pavg_mw by its OWN mean power.  tx_data='random': on every batch, behind plx_tx_qpsk_dev on make_batch's stream and
         with no read-back; 'debruijn': on the `variants` waveforms once, when the plan is made.  The patterns, tx_power,
         rx_gain and power_mw are what they are without the filter.  Not together with mux_filter (the host route).  None:
-        nothing is launched."""
+        nothing is launched.
+        wdm_receiver: None = every channel-frame of a 'sepfields' frame is picked from sample 0 and equalised with the ONE
+        CDE response at lam and disp (the error counts of the outer channels of nch > 1 frames then mean nothing: the fibre
+        gives each channel its own walk-off and its own beta2); 'channel' = every channel-frame is received at its own
+        channel's delay (sepfields_walkoff of fiber_tables' b1: GSTATE.DELAY of fiber.m:366-368, taken out as
+        RxPdmCohQpsk.m:130-151 does with x.delay = 'theory') and equalised with its own channel's dispersion (Dch of
+        fiber.m:336 at GSTATE.LAMBDA[c]) -- DESIGN.md section 8g: one plx_pick_wdm_dev launch instead of the two plx_pick_dev
+        calls, and a plx_cde_create_wdm plan.  The LO phase keeps being applied at the instants i nt/2: it is a Wiener
+        process with stationary increments, so its statistics on the shifted samples are the same.  McCampaign then returns
+        a count per channel-frame, [len(indices) * nch], as for 'unique'.  nch = 1: the delay is 0 and the table is the one
+        of wdm_receiver=None, bit for bit.  'sepfields' with frontend='pick' and equaliser='cde' only."""
         self.__dict__.update(locals())
         del self.__dict__["self"]
 
@@ -194,6 +204,17 @@ def check_config(cfg):
         raise ValueError("equaliser='dbp' has no XPM backpropagation: not with xpm_dualpol")
     if cfg.frontend not in ("pick", "cohmix"):
         raise ValueError("frontend must be 'pick' or 'cohmix'")
+    if cfg.wdm_receiver is not None:
+        if not isinstance(cfg.wdm_receiver, str) or cfg.wdm_receiver != "channel":
+            raise ValueError("wdm_receiver must be None or 'channel'")
+        if unique:
+            raise ValueError("wdm_receiver='channel' is for 'sepfields' frames: wdm_field='unique' takes its walk-off out in "
+                             "plx_wdm_select_dev")
+        if cfg.frontend == "cohmix":
+            raise ValueError("wdm_receiver='channel' needs frontend='pick' (the cohmix ADC/FIR gather takes one shift per "
+                             "polarisation)")
+        if cfg.equaliser == "dbp":
+            raise ValueError("wdm_receiver='channel' needs equaliser='cde' (equaliser='dbp' has no per-channel betat)")
     return unique, random, txfilt_on
 
 
@@ -216,6 +237,23 @@ def wdm_walkoff(shifts, beta2, b30, total_length, symbolrate, dfn, nt):
     ds = total_length * symbolrate * (beta2 * om + 0.5 * b30 * om * om)
     v = ds * nt
     return ds, (np.sign(v) * np.floor(np.abs(v) + 0.5)).astype(np.int64)
+
+
+def sepfields_walkoff(b1, total_length, symbolrate, nt):
+    """Walk-off of the channels of a 'sepfields' frame after total_length metres: (delay_symbols, delay).  b1 is
+    fiber_tables(...)["b1"], the array whose omega beta1 term is in the fibre's betat; delay_symbols[c] = total_length
+    symbolrate b1[c] (GSTATE.DELAY of fiber.m:367, summed over equal spans); delay = MATLAB's round(delay_symbols nt) in
+    samples, half away from zero, with wdm_walkoff's sign: the receiver reads the field at n + delay[c]."""
+    ds = float(total_length) * float(symbolrate) * np.atleast_1d(np.asarray(b1, dtype=float))
+    v = ds * nt
+    return ds, (np.sign(v) * np.floor(np.abs(v) + 0.5)).astype(np.int64)
+
+
+def wdm_cde_tables(N, fs, lam_nm, total_length, Dch, slope):
+    """[nch, N] complex: channel c's CDE_OFDE response cde_transfer(N, fs, lam_nm[c] 1e-9, total_length, Dch[c] 1e-6,
+    slope 1e-6), Dch = fiber_tables(...)["Dch"] (fiber.m:336): what plx_cde_create_wdm takes"""
+    return np.ascontiguousarray(np.stack([cde_transfer(N, fs, float(l) * 1e-9, total_length, float(d) * 1e-6, slope * 1e-6)
+                                          for l, d in zip(np.atleast_1d(lam_nm), np.atleast_1d(Dch))]))
 
 
 def band_limit(vx, vy, h, pavg_mw):
@@ -337,7 +375,8 @@ class HotPath:
             self.dpat_frames = torch.from_numpy(dv[np.arange(self.CF) % self.nvar].copy()).to(self.dev)
 
     def _build_rx(self, t):
-        """the receiver: a 'unique' comb's walk-off (from fiber_tables' t) and field, CDE / DBP, DSP, front end, buffers"""
+        """the receiver: a comb's walk-off (from fiber_tables' t; 'unique', or 'sepfields' with wdm_receiver='channel') and
+        'unique' field, CDE / DBP, DSP, front end, buffers"""
         torch, cfg, nch, n = self.torch, self.cfg, self.nch, self.cfg.nfft
         if self.unique:    # the walk-off select takes out, and the plan-owned field the fibre works on
             self.wdm_delay_symbols, self.wdm_delay = wdm_walkoff(self.wdm_shift, float(t["beta2"][0]), float(t["b30"]),
@@ -350,10 +389,20 @@ class HotPath:
         self.Lrx = 2 * cfg.nsymb
         fs = 2 * cfg.symbolrate * 1e9                                         # Run_my_PDM_QPSK.m:66,149
         N = min(cfg.fft_length, self.Lrx)
-        H = cde_transfer(N, fs, cfg.lam * 1e-9, cfg.length * cfg.nspans, cfg.disp * 1e-6, cfg.slope * 1e-6)
-        Hi = np.ascontiguousarray(H).view(np.float64)
         self.cde = C.c_void_p()
-        self.lib.call("plx_cde_create", C.byref(self.cde), N, cfg.cde_L, Hi.ctypes.data)
+        if cfg.wdm_receiver == "channel":
+            # every channel at its own delay and with its own dispersion.  The walk-off may exceed a
+            # frame (config[2]: ~1 140 symbols of 1 024): the frame is periodic, so the delay is taken modulo nfft here
+            self.rx_delay_symbols, delay = sepfields_walkoff(t["b1"] if nch > 1 else np.zeros(1), cfg.nspans * cfg.length,
+                                                             cfg.symbolrate, cfg.nt)
+            self.rx_delay = np.ascontiguousarray(np.sign(delay) * (np.abs(delay) % n), dtype=np.int64)
+            self.cde_H = wdm_cde_tables(N, fs, np.atleast_1d(GSTATE.LAMBDA), cfg.length * cfg.nspans, t["Dch"], cfg.slope)
+            Hi = np.ascontiguousarray(self.cde_H).view(np.float64)
+            self.lib.call("plx_cde_create_wdm", C.byref(self.cde), N, cfg.cde_L, Hi.ctypes.data, nch, 2)
+        else:
+            H = cde_transfer(N, fs, cfg.lam * 1e-9, cfg.length * cfg.nspans, cfg.disp * 1e-6, cfg.slope * 1e-6)
+            Hi = np.ascontiguousarray(H).view(np.float64)
+            self.lib.call("plx_cde_create", C.byref(self.cde), N, cfg.cde_L, Hi.ctypes.data)
         dsp = dict(workatbaudrate=False, applynlr=False, applypol=cfg.applypol, polmethod=cfg.polmethod,
                    cmaparams=dict(R=[1, 1], mu=cfg.cma_mu, taps=cfg.cma_taps, txpolars=2, phizero=0),
                    easiparams=dict(mu=cfg.cma_mu, txpolars=2, phizero=0), modorder=2, freqavg=cfg.freqavg,
@@ -634,7 +683,9 @@ class HotPath:
         return self._decide_count(F)
 
     def _front_end(self, ux, uy, rx, F, Ff, keys, lo_phase):
-        """rx [F, 2, Lrx] <- the 2-sps samples of the channel-frames ux, uy [F, nfft]: cohmix, or (channel filter +) pick + LO"""
+        """rx [F, 2, Lrx] <- the 2-sps samples of the channel-frames ux, uy [F, nfft]: cohmix, or (channel filter +) pick + LO.
+        wdm_receiver='channel': the pick reads every channel-frame at its own channel's delay; the LO phase stays at the
+        instants i half (a Wiener process has stationary increments: the same statistics on the shifted samples)."""
         cfg, st, half = self.cfg, self.stream(), self.cfg.nt // 2
         lo = lo_phase is not None or cfg.lo_linewidth > 0
         if self.front is not None:             # receiver_cohmix + ADC + decimate; ux, uy are consumed
@@ -655,9 +706,13 @@ class HotPath:
             if self.chfilt is not None:        # 'unique': the optical filter isolates the channel; ux, uy are consumed
                 for src in (ux, uy):
                     self.lib.call("plx_filter_apply_dev", self.chfilt, src.data_ptr(), F, st)
-            for pol, src in enumerate((ux, uy)):   # rx[f][pol][i] = scale * u_pol[f][i*half]
-                self.lib.call("plx_pick_dev", src.data_ptr(), rx.data_ptr() + pol * self.Lrx * 16, cfg.nfft, self.Lrx, 0,
-                              half, self.rx_scale, F, 2 * self.Lrx, st)
+            if cfg.wdm_receiver == "channel":  # rx[cf][pol][i] = scale * u_pol[cf][(i*half + rx_delay[c]) mod nfft], one launch
+                self.lib.call("plx_pick_wdm_dev", ux.data_ptr(), uy.data_ptr(), rx.data_ptr(), cfg.nfft, self.Lrx, half,
+                              self.rx_scale, self.nch, Ff, self.rx_delay.ctypes.data, st)
+            else:
+                for pol, src in enumerate((ux, uy)):   # rx[f][pol][i] = scale * u_pol[f][i*half]
+                    self.lib.call("plx_pick_dev", src.data_ptr(), rx.data_ptr() + pol * self.Lrx * 16, cfg.nfft, self.Lrx, 0,
+                                  half, self.rx_scale, F, 2 * self.Lrx, st)
             if lo:                             # the LO at the pick instants: rx[f][pol][i] *= exp(-i phi_b[f][i half])
                 self._phase(rx.data_ptr(), rx.data_ptr() + self.Lrx * 16, half, 2 * self.Lrx, -1.0, Ff, keys,
                             _abi.PLX_PHASE_LO, cfg.lo_linewidth, lo_phase)
@@ -863,7 +918,8 @@ class McCampaign(_Simulate):
             side = rxs if rxs is self._rx_stream else None
             hp.receive(ux, uy, self.sigma, MASTER_SEED, side, idx)   # receiver noise keyed by realisation index
             with torch.cuda.stream(rxs):
-                ncf = n * hp.nch if hp.unique else n    # a 'unique' comb: a count per channel-frame, [n nch], channels innermost
+                # a 'unique' comb, or 'sepfields' with wdm_receiver='channel': a count per channel-frame, [n nch], channels innermost
+                ncf = n * hp.nch if hp.unique or hp.cfg.wdm_receiver == "channel" else n
                 v = hp.evm(ncf)            # a continuous per-realisation sample (mc_estimate) beside the error count
                 e = hp.errors(ncf)
                 if side is not None:
@@ -877,7 +933,8 @@ class McCampaign(_Simulate):
 
     def collect(self, handle, with_samples=False):
         """int64 error counts of a launch() handle (and, with_samples, the float64 EVM samples beside them); with
-        wdm_field='unique' one per channel-frame: [len(indices) * nch], the channels of a realisation side by side"""
+        wdm_field='unique' or wdm_receiver='channel' one per channel-frame: [len(indices) * nch], the channels of a realisation
+        side by side"""
         res, smp = [], []
         for e, v, done in handle or []:
             done.synchronize()             # the counts were formed on the receiver's stream
