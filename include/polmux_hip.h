@@ -224,7 +224,8 @@ int plx_scalar_ssfm(double *ur, double *ui, const plx_ssfm_desc *desc, double *f
 /* adaptive step size by local error (x.ltol): tolflag 2 = [firstdz,ncycle,u]=scalar_a_ssfm(...) with adaptssfm
  * (fiber.m:639-679, 938-1009); tolflag 1 = x.dphiadapt: adaptive first step, then the constant-phase loop with
  * the corrected dphimax (fiber.m:588-611).  trg.err = ltol, trg.safety = 0.9 in fiber.m:145-146.  Scalar fields
- * only: a dual-polarisation descriptor returns PLX_ERR_REFERENCE with the message of fiber.m:374.               */
+ * only: a dual-polarisation descriptor returns PLX_ERR_REFERENCE with the message of fiber.m:374.  tolflag 1 with
+ * alphalin == 0 returns PLX_ERR_REFERENCE too: the corrected dphimax of fiber.m:607 is 0/0 in a lossless fibre.   */
 int plx_scalar_ssfm_adaptive(double *ur, double *ui, const plx_ssfm_desc *desc, int tolflag, double ltol,
                              double safety, double *firstdz, int32_t *ncycle, int32_t *nrej);
 

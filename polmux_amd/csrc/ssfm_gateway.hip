@@ -168,6 +168,11 @@ extern "C" int plx_scalar_ssfm_adaptive(double *ur, double *ui, const plx_ssfm_d
     if (!ur || !ui || !desc) PLX_FAIL(PLX_ERR_ARG, "plx_scalar_ssfm_adaptive: null argument");
     if (desc->dual_pol) PLX_FAIL(PLX_ERR_REFERENCE, "adaptive step available in absence of polarization effects"); // fiber.m:374
     if (tolflag != 1 && tolflag != 2) PLX_FAIL(PLX_ERR_ARG, "plx_scalar_ssfm_adaptive: tolflag must be 1 or 2");
+    // the correction of dphimax after the adaptive first step (fiber.m:607) is 0/0 in a lossless fibre: the reference goes
+    // on with dphimax = NaN and returns a field of NaN; refused here, before any device work
+    if (tolflag == 1 && desc->alphalin == 0)
+        PLX_FAIL(PLX_ERR_REFERENCE, "plx_scalar_ssfm_adaptive: x.dphiadapt needs a fibre with loss: the corrected dphimax "
+                                    "(1-exp(-alphalin*zprop))/(1-exp(-alphalin*dzini)) of fiber.m:607 is 0/0 at alphalin = 0");
     plx_ssfm_desc d = *desc;
     d.max_frames = 1;
     // plan, the three field copies of adaptssfm and the staging area come from the library's gateway workspace
