@@ -369,6 +369,12 @@ int plx_dsp_create(plx_dsp **plan, int64_t Lin, int32_t ncol, int32_t max_frames
 int plx_dsp_destroy(plx_dsp *plan);
 /* d_in [frame][ncol][Lin] -> d_out [frame][ncol][Lout], Lout = Lin or ceil(Lin/2)  */
 int plx_dsp_run_dev(plx_dsp *plan, const double *d_in, double *d_out, int nframes, void *stream);
+/* plx_dsp_run_dev that also reads out the frequency estimate: d_turns int32 [frame][ncol] = round((omega(end) - omega(1))
+ * / 2 pi) of the circularity fix (DspPdmCohQpsk.m:52-55), the whole turns the estimated carrier phase makes over the frame
+ * (minus the LO offset in bins while that is inside the estimator's range, L / 2^(modorder + 1) symbols); 0 when freqavg
+ * == 0.  Stored by one thread of the carrier-recovery kernel from the value it forms anyway: the symbols are bit-identical
+ * with and without the pointer.  d_turns == NULL: plx_dsp_run_dev.                                                    */
+int plx_dsp_run_freq_dev(plx_dsp *plan, const double *d_in, double *d_out, int nframes, int32_t *d_turns, void *stream);
 int64_t plx_dsp_out_len(const plx_dsp *plan);
 
 /* samp2pat 'coherent' decisions (samp2pat.m:61-66) + error count against the
@@ -427,6 +433,32 @@ int plx_ampliflat_dev(double *d_ux, double *d_uy, int64_t nfft, int32_t nfc, int
 int plx_phase_noise_dev(double *d_ux, double *d_uy, int64_t stride, int64_t pitch, double sign, int64_t nfft,
                         int32_t nfc, int nframes, const double *sigma, uint64_t seed, const int64_t *d_keys,
                         int32_t tag, const double *d_phi_in, double *d_phi_out, double *d_work, void *stream);
+
+/* ------------------------------------------------------------ LO frequency offset --- */
+/* The detuned local oscillator of receiver_cohmix.m:188-200 (x.lodetuning) with an offset of its own per (frame, channel),
+ * in integer frequency bins b (one bin = symbolrate / nsymb):
+ *   d_bins_in given (int32 [frame][nfc], the injected route): b = d_bins_in[f nfc + c]; k0 and kspread are ignored.
+ *   otherwise b = k0 + d: d = 0 when kspread == 0, else d = (int64)(((uint64)r0 * (uint64)(2 kspread + 1)) >> 32) - kspread,
+ *     uniform on -kspread .. kspread, r0 the first word of ONE Philox-4x32-10 call with counter (0, 0, c,
+ *     PLX_PHILOX_LO_DETUNE) and the key plx_phase_noise_dev documents, K = d_keys[f] or f.  Pure integer arithmetic.
+ *     Counter word 3 = 5 is a stream of its own: ASE uses 0 and 1, the lasers 2 and 3, the data 4.
+ *   theta[f][c][n] = 2 pi (((b mod nfft) (n + 1)) mod nfft) / nfft, n < nfft: the index is 1-based as in
+ *     receiver_cohmix.m:197, b mod nfft is in [0, nfft) for either sign, and the product is reduced in 64-bit integers, so
+ *     the one rounding of theta does not grow with n or b.
+ * Outputs (any of them, at least one):
+ *   d_ux [, d_uy]: u[(f nfc + c) pitch + j] *= exp(i sign theta[f][c][j stride]), j < nfft / stride -- the conventions of
+ *                  plx_phase_noise_dev (sign -1, stride NT/2 on the 2-sps receiver samples: the LO seen at the pick instants)
+ *   d_phi:         float64 [frame][nfc][nfft], 16-byte aligned: = theta, or += theta when phi_accumulate (the buffer
+ *                  plx_front_run_lo_dev reads; with accumulate, a Wiener phase already in it stays)
+ *   d_bins_out:    int32 [frame][nfc] = b
+ * PLX_ERR_ARG before any launch: nfft no power of two in [256, 2^20]; nfc outside [1, 64]; nframes < 1; no output; d_uy
+ * without d_ux; with d_ux, stride < 1 or not dividing nfft or pitch < nfft / stride; d_phi not 16-byte aligned; on the
+ * generated route kspread < 0, 2 kspread + 1 > nfft or |k0| > 2^30.
+ * No allocation, no copy, no synchronisation: ONE launch on `stream`, a grid of at most 2048 workgroups.               */
+#define PLX_PHILOX_LO_DETUNE 5
+int plx_lo_detune_dev(double *d_ux, double *d_uy, int64_t stride, int64_t pitch, double sign, int64_t nfft, int32_t nfc,
+                      int nframes, int64_t k0, int64_t kspread, uint64_t seed, const int64_t *d_keys,
+                      const int32_t *d_bins_in, double *d_phi, int32_t phi_accumulate, int32_t *d_bins_out, void *stream);
 
 /* ------------------------------------------------------- PDM-QPSK transmitter --- */
 /* The reference's Tx chain (electricsource 'cosroll' -> qi_modulator -> create_field(..., power 'average')) on random

@@ -23,6 +23,7 @@ PLX_DBP_STREAMED = 1
 PLX_PHASE_TX = 2
 PLX_PHASE_LO = 3
 PLX_PHILOX_TX_DATA = 4
+PLX_PHILOX_LO_DETUNE = 5
 
 
 class PolmuxError(RuntimeError):
@@ -127,6 +128,7 @@ SIGNATURES = {
     "plx_dsp_create": [C.POINTER(_vp), _i64, _i32, _i32, C.POINTER(DspParams)],
     "plx_dsp_destroy": [_vp],
     "plx_dsp_run_dev": [_vp, _vp, _vp, C.c_int, _vp],
+    "plx_dsp_run_freq_dev": [_vp, _vp, _vp, C.c_int, _vp, _vp],
     "plx_dsp_out_len": [_vp],
     "plx_decide_count_dev": [_vp, _i64, _i32, C.c_int, _vp, _vp, _vp, _vp],
     "plx_decide_count_frames_dev": [_vp, _i64, _i32, C.c_int, _vp, _i64, _vp, _vp, _vp],
@@ -135,6 +137,8 @@ SIGNATURES = {
     "plx_ampliflat_dev": [_vp, _vp, _i64, _i32, C.c_int, _dbl, _vp, _vp, C.c_uint64, _vp, _i32, _i32, _vp],
     "plx_phase_noise_dev": [_vp, _vp, _i64, _i64, _dbl, _i64, _i32, C.c_int, _vp, C.c_uint64, _vp, _i32, _vp, _vp, _vp,
                             _vp],
+    "plx_lo_detune_dev": [_vp, _vp, _i64, _i64, _dbl, _i64, _i32, C.c_int, _i64, _i64, C.c_uint64, _vp, _vp, _vp, _i32, _vp,
+                          _vp],
     "plx_tx_qpsk_dev": [_vp, _vp, _i64, _i32, _i32, C.c_int, _vp, _dbl, C.c_uint64, _vp, _vp, _vp, _vp, _vp],
     "plx_wdm_mux_dev": [_vp, _vp, _vp, _vp, _i64, _i32, C.c_int, _vp, _vp],
     "plx_wdm_select_dev": [_vp, _vp, _vp, _vp, _i64, _i32, C.c_int, _vp, _vp, _vp],

@@ -598,6 +598,7 @@ struct CpeArgs {
     double *wsr;     // global scratch [frame*ncol][L]
     int64_t L;
     int use_lds, modorder, freqavg, phasavg, poworder;
+    int32_t *turns;  // [frame][ncol] whole turns of the frequency estimate (plx_dsp_run_freq_dev; null: not stored)
 };
 
 __device__ __forceinline__ cplx cpow_int(cplx v, int P)
@@ -681,13 +682,16 @@ __global__ __launch_bounds__(256) void k_cpe(CpeArgs a)
         block_cumsum(w, L, red, tid, nthr);
         // circularity fix :52-55
         const double w1 = w[0], wend = w[L - 1];
-        const double closest = w1 + round((wend - w1) / 2 / 3.14159265358979323846) * 2 * 3.14159265358979323846;
+        const double nturns = round((wend - w1) / 2 / 3.14159265358979323846);
+        const double closest = w1 + nturns * 2 * 3.14159265358979323846;
         const double ratio = closest / wend;
+        if (a.turns && tid == 0) a.turns[col] = (int32_t)nturns;
         __syncthreads();
         for (int64_t n = tid; n < L; n += nthr) w[n] = ((w[n] - w1) * ratio) + w1;
         __syncthreads();
     } else {
         for (int64_t n = tid; n < L; n += nthr) w[n] = 0;
+        if (a.turns && tid == 0) a.turns[col] = 0;
         __syncthreads();
     }
     // theta = vitvit(sigdemod, P, M, phasavg, true)  :57-61
@@ -1316,6 +1320,11 @@ static int demux_stage(plx_dsp *P, int method, cplx *src, cplx *dst, int nframes
 
 extern "C" int plx_dsp_run_dev(plx_dsp *P, const double *d_in, double *d_out, int nframes, void *stream)
 {
+    return plx_dsp_run_freq_dev(P, d_in, d_out, nframes, nullptr, stream);
+}
+
+extern "C" int plx_dsp_run_freq_dev(plx_dsp *P, const double *d_in, double *d_out, int nframes, int32_t *d_turns, void *stream)
+{
     if (!P || !d_in || !d_out) PLX_FAIL(PLX_ERR_ARG, "plx_dsp_run_dev: null argument");
     if (nframes < 1 || nframes > P->max_frames) PLX_FAIL(PLX_ERR_ARG, "plx_dsp_run_dev: nframes out of range");
     const plx_dsp_params &p = P->p;
@@ -1353,6 +1362,7 @@ extern "C" int plx_dsp_run_dev(plx_dsp *P, const double *d_in, double *d_out, in
     CpeArgs ca;
     ca.s = cur; ca.out = (cplx *)d_out; ca.wsc = P->d_wsc; ca.wsr = P->d_wsr; ca.L = P->L; ca.use_lds = P->use_lds;
     ca.modorder = p.modorder; ca.freqavg = p.freqavg; ca.phasavg = p.phasavg; ca.poworder = p.poworder;
+    ca.turns = d_turns;
     PLX_LAUNCH(k_cpe, dim3((unsigned)(nframes * P->ncol)), dim3(256), P->lds_cpe, stream, ca);
     PLX_HIP(hipGetLastError());
     return PLX_OK;

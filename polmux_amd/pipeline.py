@@ -10,6 +10,7 @@ torch only owns the HBM buffers and the stream.
 """
 import ctypes as C
 import math
+import warnings
 
 import numpy as np
 
@@ -55,7 +56,7 @@ class HotPathConfig:
                  adcbits=5, span_nf_db=None, rx_amp=False, variants=1, nch=1, chspacing=0.4, share_device=False,
                  equaliser="cde", dbp_steps=4, dbp_xi=1.0, tx_linewidth=0.0, lo_linewidth=0.0, decoding="rotation",
                  xpm_dualpol=None, wdm_field="sepfields", mux_filter=None, tx_data="debruijn",
-                 tx_filter=None, wdm_receiver=None):
+                 tx_filter=None, wdm_receiver=None, lo_detuning=0.0, lo_detuning_spread=0.0):
         """frontend: 'pick' = 2-sps sampling supplied by the harness; 'cohmix' = the reference's own
         receiver_cohmix + ADC + decimate chain (RxPdmCohQpsk.m, Run_my_PDM_QPSK.m:52-73 defaults) on the device.
         nspans > 1: every span but the last is followed by an in-line flat amplifier restoring its loss
@@ -119,7 +120,16 @@ class HotPathConfig:
         calls, and a plx_cde_create_wdm plan.  The LO phase keeps being applied at the instants i nt/2: it is a Wiener
         process with stationary increments, so its statistics on the shifted samples are the same.  McCampaign then returns
         a count per channel-frame, [len(indices) * nch], as for 'unique'.  nch = 1: the delay is 0 and the table is the one
-        of wdm_receiver=None, bit for bit.  'sepfields' with frontend='pick' and equaliser='cde' only."""
+        of wdm_receiver=None, bit for bit.  'sepfields' with frontend='pick' and equaliser='cde' only.
+        lo_detuning, lo_detuning_spread: the LO's frequency offset from its channel's carrier in Hz (receiver_cohmix.m
+        x.lodetuning).  With minfreq = symbolrate 1e9 / nsymb, k0 = floor(lo_detuning / minfreq) (the
+        reference's floor, :191-192, also for negative values) and K = floor(lo_detuning_spread / minfreq): the LO of every
+        channel-frame sits k0 + d bins off, d uniform on -K .. K, drawn on the device (plx_lo_detune_dev) under the keys the
+        LO's phase noise uses (noise_keys, or the frame index) and the channel -- a realisation's offset does not depend on
+        batching or sharding; HotPath.lo_bins_host states it on the host.  The LO multiplies the hybrid's LO field (cohmix)
+        or acts as exp(-i theta) on the picked 2-sps samples (pick); the frequency estimator of DspPdmCohQpsk follows it
+        while |k0| + K < nsymb / 8, and HotPath.freq_turns reads its estimate out.  Not with equaliser='dbp'.  Both 0:
+        nothing is launched."""
         self.__dict__.update(locals())
         del self.__dict__["self"]
 
@@ -185,9 +195,44 @@ def check_tx_options(cfg):
     return td == "random"
 
 
+def lo_detune_bins(cfg):
+    """(k0, K): lo_detuning and lo_detuning_spread in bins of minfreq = symbolrate 1e9 / nsymb, both floored as
+    receiver_cohmix.m:191-192 floors x.lodetuning (towards -inf: -0.5 bins is bin -1)"""
+    minfreq = cfg.symbolrate * 1e9 / cfg.nsymb
+    return math.floor(float(cfg.lo_detuning) / minfreq), math.floor(float(cfg.lo_detuning_spread) / minfreq)
+
+
+def check_lo_detuning(cfg):
+    """The raises and warnings of HotPathConfig's lo_detuning / lo_detuning_spread (needs no GPU); returns True when
+    either is non-zero."""
+    for name in ("lo_detuning", "lo_detuning_spread"):
+        v = getattr(cfg, name)
+        if isinstance(v, (bool, str, bytes)) or np.ndim(v) != 0 or not math.isfinite(float(v)):
+            raise ValueError("%s must be a finite scalar (Hz)" % name)
+    if float(cfg.lo_detuning_spread) < 0:
+        raise ValueError("lo_detuning_spread must be >= 0 (Hz)")
+    if not (float(cfg.lo_detuning) or float(cfg.lo_detuning_spread)):
+        return False
+    if cfg.equaliser == "dbp":
+        raise ValueError("lo_detuning / lo_detuning_spread: not with equaliser='dbp' (backpropagating a displaced spectrum is "
+                         "wrong, and no frequency estimator runs in front of DBP)")
+    k0, K = lo_detune_bins(cfg)
+    if 2 * K + 1 > cfg.nfft:
+        raise ValueError("lo_detuning_spread: the 2 K + 1 = %d offsets do not fit the %d bins of a frame" % (2 * K + 1, cfg.nfft))
+    if abs(k0) > 2 ** 30:
+        raise ValueError("lo_detuning: more than 2^30 bins")
+    if float(cfg.lo_detuning) and k0 == 0:       # receiver_cohmix.m:193-196
+        warnings.warn("lo_detuning is below one frequency bin (symbolrate / nsymb): the LO detuning is set to 0 bins")
+    if cfg.freqavg > 0 and abs(k0) + K >= cfg.nsymb / 8:
+        warnings.warn("LO offsets up to %d bins reach the range of the QPSK frequency estimator, nsymb / 8 = %g bins: "
+                      "beyond it the estimate aliases by nsymb / 4" % (abs(k0) + K, cfg.nsymb / 8))
+    return True
+
+
 def check_config(cfg):
     """Every raise of HotPathConfig's options (needs no GPU, no library, no torch); returns (unique, random, txfilt_on)."""
     unique, random, txfilt_on = check_wdm_options(cfg), check_tx_options(cfg), check_tx_filter(cfg)
+    check_lo_detuning(cfg)
     if cfg.equaliser not in ("cde", "dbp"):
         raise ValueError("equaliser must be 'cde' or 'dbp'")
     if cfg.equaliser == "dbp" and cfg.frontend != "pick":
@@ -266,6 +311,8 @@ def band_limit(vx, vy, h, pavg_mw):
 class HotPath:
     def __init__(self, cfg, max_frames):
         self.unique, self.random, self.txfilt_on = check_config(cfg)
+        self.lo_k0, self.lo_K = lo_detune_bins(cfg)      # the LO's offset in bins: k0 + a draw on -K .. K per channel-frame
+        self.detune = bool(float(cfg.lo_detuning) or float(cfg.lo_detuning_spread))
         # every handle and optional component, so that close() can run on a half-built plan
         self.ssfm = self.cde = self.dsp = self.chfilt = self.txfilt = self.dbp = self.front = None
         self.cfg = cfg
@@ -386,6 +433,8 @@ class HotPath:
             self.wy = torch.empty_like(self.wx)
         self._phase_work = {}                            # tile sums of the phase generator, per laser (allocated on use)
         self._lo_buf = None                              # [F nch, nfft] LO phase of the cohmix route (allocated on use)
+        self._lo_bins = self._turns = None               # the last receive()'s LO offsets [CF] and frequency estimates [CF, 2]
+        self._detuned = 0                                # channel-frames of the last receive() if its LO was detuned
         self.Lrx = 2 * cfg.nsymb
         fs = 2 * cfg.symbolrate * 1e9                                         # Run_my_PDM_QPSK.m:66,149
         N = min(cfg.fft_length, self.Lrx)
@@ -537,6 +586,25 @@ class HotPath:
         return np.stack([np.stack([synth.random_qpsk_bits(self.cfg.nsymb, MASTER_SEED, int(k), c) for c in range(self.nch)])
                          for k in keys])
 
+    def lo_bins_host(self, keys):
+        """[len(keys), nch] int64: the LO offsets in bins that lo_detuning / lo_detuning_spread give the realisations `keys`
+        (the host mirror synth.lo_detune_bins of plx_lo_detune_dev's draw)"""
+        return synth.lo_detune_bins(MASTER_SEED, keys, self.nch, self.lo_k0, self.lo_K)
+
+    @property
+    def lo_bins(self):
+        """int32 device tensor [CF]: the LO offset in bins of every channel-frame of the last receive() (None if its LO was
+        not detuned)"""
+        return self._lo_bins[:self._detuned] if self._detuned else None
+
+    def freq_turns(self, F):
+        """int32 device tensor [F, 2]: round((omega(end) - omega(1)) / 2 pi) of the frequency estimator (DspPdmCohQpsk.m:
+        52-55) on both polarisations of the first F channel-frames of the last receive() -- minus the LO's offset in bins
+        while that is within the estimator's range.  Read out only when the LO was detuned (plx_dsp_run_freq_dev)."""
+        if not self._detuned:
+            raise ValueError("freq_turns: the last receive() ran without lo_detuning, lo_detuning_spread or lo_bins")
+        return self._turns[:F]
+
     def set_random_pmd(self, seeds):
         """brf draws of fiber.m:274-276, one independent set per frame, keyed by the realisation index alone (a
         counter-based generator: splitmix64 of (master seed, realisation, plate, stream) -> U[0,1)), so any batching
@@ -644,7 +712,8 @@ class HotPath:
         """per-frame errors by cfg.decoding: errors_resolved ('rotation') or errors_dqpsk ('dqpsk')"""
         return self.errors_dqpsk(F) if self.cfg.decoding == "dqpsk" else self.errors_resolved(F)
 
-    def receive(self, ux, uy, noise_sigma=0.0, noise_seed=None, side_stream=None, noise_keys=None, lo_phase=None):
+    def receive(self, ux, uy, noise_sigma=0.0, noise_seed=None, side_stream=None, noise_keys=None, lo_phase=None,
+                lo_bins=None):
         """Front end (2-sps pick, or receiver_cohmix + ADC + decimate), CDE, DSP, decisions.  Returns err [F,2] (device).
         Receiver noise (sigma per quadrature on the 2-sps samples, an ASE stand-in) comes from the device Philox
         generator of plx_ampliflat_dev keyed by (noise_seed, noise_keys[frame] or frame): with noise_keys = the
@@ -652,21 +721,27 @@ class HotPath:
         With side_stream the whole receiver is enqueued on that stream behind the fibre of this batch, so
         the latency-bound CMA recurrence overlaps the HBM-bound fibre sweeps of the NEXT batch.
         lo_phase: optional [F, nch, n] float64 device tensor, the LO phase of each channel's receiver used INSTEAD of the
-        cfg.lo_linewidth generator (keyed by noise_keys, or the frame index)."""
+        cfg.lo_linewidth generator (keyed by noise_keys, or the frame index).
+        lo_bins: optional [F, nch] int32 device tensor, the LO's frequency offset of each channel's receiver in bins used
+        INSTEAD of cfg.lo_detuning / lo_detuning_spread (the parity route; not with equaliser='dbp')."""
         if side_stream is not None and self.overlap_ok():
             torch = self.torch
             ready = torch.cuda.Event()
             ready.record(torch.cuda.current_stream())
             side_stream.wait_event(ready)
             with torch.cuda.stream(side_stream):
-                return self.receive(ux, uy, noise_sigma, noise_seed, None, noise_keys, lo_phase)
+                return self.receive(ux, uy, noise_sigma, noise_seed, None, noise_keys, lo_phase, lo_bins)
         F = ux.shape[0] * self.nch             # channel-frames: every channel of a 'sepfields' frame has its own receiver
         cfg, st, rx = self.cfg, self.stream(), self.rx[:F]
         if self.nch > 1:
             ux, uy = ux.view(F, cfg.nfft), uy.view(F, cfg.nfft)
         Ff = F // self.nch                     # frames (the phase tensors are [Ff, nch, nfft])
         keys = frame_keys(noise_keys, Ff, "noise_keys")
-        self._front_end(ux, uy, rx, F, Ff, keys, lo_phase)
+        detuned = self.detune or lo_bins is not None
+        if detuned:
+            self._detune_buffers(lo_bins, Ff)
+        self._detuned = F if detuned else 0
+        self._front_end(ux, uy, rx, F, Ff, keys, lo_phase, lo_bins)
         if self.rx_gain is not None and self.front is None:   # launch-power ladder: each frame normalised by its own power
             rx.mul_(self.rx_gain[:F])
         if noise_sigma:
@@ -679,16 +754,58 @@ class HotPath:
             self.dbp.apply(rx, self.eq, sc, st)
         else:
             self.lib.call("plx_cde_apply_dev", self.cde, rx.data_ptr(), self.eq.data_ptr(), self.Lrx, 2 * F, st)
-        self.lib.call("plx_dsp_run_dev", self.dsp, self.eq.data_ptr(), self.sym.data_ptr(), F, st)
+        if detuned:                            # the same DSP, with the frequency estimate of every column read out
+            self.lib.call("plx_dsp_run_freq_dev", self.dsp, self.eq.data_ptr(), self.sym.data_ptr(), F, self._turns.data_ptr(), st)
+        else:
+            self.lib.call("plx_dsp_run_dev", self.dsp, self.eq.data_ptr(), self.sym.data_ptr(), F, st)
         return self._decide_count(F)
 
-    def _front_end(self, ux, uy, rx, F, Ff, keys, lo_phase):
+    def _detune_buffers(self, lo_bins, Ff):
+        """the plan's buffers of a detuned receive() (allocated on use), and the checks of an injected lo_bins"""
+        torch = self.torch
+        if lo_bins is not None:
+            if self.dbp is not None:
+                raise ValueError("lo_bins: not with equaliser='dbp'")
+            if tuple(lo_bins.shape) != (Ff, self.nch) or lo_bins.dtype != torch.int32 or not lo_bins.is_contiguous() \
+                    or lo_bins.device != self.dev:
+                raise ValueError("injected lo_bins must be a contiguous int32 device tensor [F, nch] = [%d, %d]" % (Ff, self.nch))
+        if self._lo_bins is None:
+            self._lo_bins = torch.zeros(self.CF, dtype=torch.int32, device=self.dev)
+            self._turns = torch.zeros((self.CF, 2), dtype=torch.int32, device=self.dev)
+
+    def _lo_detune(self, pu, pv, stride, pitch, sign, Ff, keys, lo_bins, phi, accumulate):
+        """one plx_lo_detune_dev call on Ff frames of nch channels: the injected lo_bins, or k0 + the draw keyed by keys;
+        the offsets go to self._lo_bins"""
+        kt = None if lo_bins is not None else self._keys_dev(keys)
+        self.lib.call("plx_lo_detune_dev", pu, pv, stride, pitch, sign, self.cfg.nfft, self.nch, Ff, self.lo_k0, self.lo_K,
+                      MASTER_SEED, kt.data_ptr() if kt is not None else None,
+                      lo_bins.data_ptr() if lo_bins is not None else None, phi, int(accumulate), self._lo_bins.data_ptr(),
+                      self.stream())
+
+    def _front_end(self, ux, uy, rx, F, Ff, keys, lo_phase, lo_bins=None):
         """rx [F, 2, Lrx] <- the 2-sps samples of the channel-frames ux, uy [F, nfft]: cohmix, or (channel filter +) pick + LO.
         wdm_receiver='channel': the pick reads every channel-frame at its own channel's delay; the LO phase stays at the
         instants i half (a Wiener process has stationary increments: the same statistics on the shifted samples)."""
         cfg, st, half = self.cfg, self.stream(), self.cfg.nt // 2
         lo = lo_phase is not None or cfg.lo_linewidth > 0
-        if self.front is not None:             # receiver_cohmix + ADC + decimate; ux, uy are consumed
+        detuned = self.detune or lo_bins is not None
+        if self.front is not None and detuned:
+            # the detuned LO of receiver_cohmix.m:197-203, :227: Elo[cf] = Elo exp(i (theta[cf] + phi_b[cf])) -- the Wiener
+            # phase (generated, or an injected one copied in) is in the plan's buffer first and theta is added to it
+            if self.rx_gain is not None:
+                ux.mul_(self.rx_gain[:F, :, 0])
+                uy.mul_(self.rx_gain[:F, :, 0])
+            if self._lo_buf is None:
+                self._lo_buf = self.torch.empty((self.CF, cfg.nfft), dtype=self.torch.float64, device=self.dev)
+            lop = self._lo_buf
+            if lo_phase is not None:
+                self._phase_shape(lo_phase, Ff)
+                lop[:F].copy_(lo_phase.view(F, cfg.nfft))
+            elif lo:
+                self._phase(None, None, 1, cfg.nfft, 1.0, Ff, keys, _abi.PLX_PHASE_LO, cfg.lo_linewidth, None, lop.data_ptr())
+            self._lo_detune(None, None, 1, cfg.nfft, 1.0, Ff, keys, lo_bins, lop.data_ptr(), lo)
+            self.front.run(ux, uy, self.front_shifts, out=rx, lo_phase=lop)
+        elif self.front is not None:           # receiver_cohmix + ADC + decimate; ux, uy are consumed
             if self.rx_gain is not None:       # launch-power ladder: each frame normalised by its own power
                 ux.mul_(self.rx_gain[:F, :, 0])
                 uy.mul_(self.rx_gain[:F, :, 0])
@@ -716,6 +833,9 @@ class HotPath:
             if lo:                             # the LO at the pick instants: rx[f][pol][i] *= exp(-i phi_b[f][i half])
                 self._phase(rx.data_ptr(), rx.data_ptr() + self.Lrx * 16, half, 2 * self.Lrx, -1.0, Ff, keys,
                             _abi.PLX_PHASE_LO, cfg.lo_linewidth, lo_phase)
+            if detuned:                        # its frequency offset there: rx[cf][pol][i] *= exp(-i theta[cf][i half])
+                self._lo_detune(rx.data_ptr(), rx.data_ptr() + self.Lrx * 16, half, 2 * self.Lrx, -1.0, Ff, keys, lo_bins,
+                                None, False)
 
     def _rx_noise(self, rx, F, Ff, noise_sigma, noise_seed, keys):
         """noise of sigma per quadrature on the 2-sps samples rx [F, 2, Lrx], keyed by (noise_seed, keys[frame] or channel-frame)"""

@@ -163,6 +163,29 @@ def random_qpsk_bits(nsymb, seed, key, chan):
     return np.stack([(w[(m >> np.uint64(5)).astype(np.int64)] >> sh) & np.uint64(1) for w in r], 1).astype(np.uint8)
 
 
+PHILOX_LO_DETUNE = 5
+
+
+def lo_detune_bins(seed, keys, nch, k0, kspread):
+    """[len(keys), nch] int64: the LO offsets in bins plx_lo_detune_dev gives the channels of the realisations `keys` under
+    `seed` -- k0 + d, d = ((r0 (2 kspread + 1)) >> 32) - kspread with r0 the first word of one Philox call with counter
+    (0, 0, channel, 5) and the library's key derivation (include/polmux_hip.h); d = 0 when kspread == 0."""
+    keys = [int(k) for k in keys]
+    out = np.full((len(keys), nch), int(k0), dtype=np.int64)
+    if kspread == 0:
+        return out
+    c = np.arange(nch, dtype=np.uint64)
+    zero = np.zeros(nch, np.uint64)
+    for i, key in enumerate(keys):
+        with np.errstate(over="ignore"):
+            s, k = np.uint64(int(seed) & (2 ** 64 - 1)), np.uint64(key & (2 ** 64 - 1))
+            key0 = (s ^ k) & _M32
+            key1 = ((s >> np.uint64(32)) ^ ((k * np.uint64(0x9E3779B97F4A7C15)) >> np.uint64(32))) & _M32
+        r0 = _philox4x32(zero, zero, c, np.full(nch, PHILOX_LO_DETUNE, np.uint64), key0, key1)[0]
+        out[i] += ((r0 * np.uint64(2 * int(kspread) + 1)) >> np.uint64(32)).astype(np.int64) - int(kspread)
+    return out
+
+
 # --------------------------------------------------------------- fiber.m tables ---
 CLIGHT = 299792458.0                                    # reset_all.m:105
 
